@@ -32,14 +32,25 @@ default run is cfg2):
   (test_time=True, perturb=0, noise_std=0, chunks of 32768 rays).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2]
+                    [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...
 
 Prints ONE JSON line (rank 0).  ``value`` = rays/s over all ranks (camera rays
-for cfg5).  The ``roofline`` object is for the dominant kernel, timed with HIP
-events around each of its launches inside the timed region; ``cpu_baseline``
-times the CPU oracle (the reference algorithm restated in PyTorch-CPU, pinned
-to the reference by tests/golden) on a bounded sample of the same workload on
-this host's cores.
+for cfg5), ``ms_per_step`` the milliseconds one of the K timed steps took.  The
+``roofline`` object is for the dominant kernel, timed with HIP events around
+each of its launches inside the timed region.
+
+A plain run sets up, runs W untimed and K timed steps, writes the last timed
+step's outputs when ``--dump-outputs DIR`` is given (``DIR/<name>.npy``: the
+render results the step's caller receives, its loss and both models' updated
+parameters; the same arguments give the same inputs in every run) and prints
+the line.  What takes runs of its own is behind ``--full``: the per-kernel
+rooflines with the two passes serialised (10 extra steps), the exact-fp32 leg
+(``fp32_leg``) and ``cpu_baseline`` / ``cpu_baseline_1thread``, which time the
+CPU oracle (the reference algorithm restated in PyTorch-CPU, pinned to the
+reference by tests/golden) on a bounded sample of the same workload on this
+host's cores.  Without ``--full`` those fields are null and ``rooflines`` is
+the timed region's.
 """
 from __future__ import annotations
 
@@ -109,6 +120,35 @@ KERNEL_FLOP = {"mlp_fwd": FLOP_FWD, "mlp_fwd_sigma": FLOP_FWD_SIGMA,
                "mlp_bwd_dgrad": FLOP_DGRAD, "mlp_bwd_dgrad_sigma": FLOP_DGRAD_SIGMA,
                "mlp_wgrad": FLOP_WGRAD, "mlp_wgrad_sigma": FLOP_FWD_SIGMA}
 CONFIGS = ("cfg2", "cfg3", "cfg4", "cfg5", "eval")
+DUMP_LIMIT_BYTES = 64 * 10**6      # --dump-outputs: all files together
+
+
+def dump_outputs(out_dir, arrays, limit_bytes=DUMP_LIMIT_BYTES):
+    """--dump-outputs: write every tensor of ``arrays`` (name -> tensor) as
+    ``out_dir/<name>.npy``, float32 (float64 tensors stay float64).  When all of
+    them exceed ``limit_bytes``, each array larger than an equal share of the
+    limit is cut to a fixed sample of its flattened elements (sorted indices
+    drawn from a generator seeded with 0: the same elements in every run).
+    Returns name -> (shape written, elements of the whole array)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    host = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        host[name] = t.to("cpu", torch.float64 if t.dtype == torch.float64 else torch.float32).numpy()
+    share = None
+    if sum(v.nbytes for v in host.values()) > limit_bytes:
+        share = limit_bytes // max(1, len(host))
+    written = {}
+    for name, v in sorted(host.items()):
+        total = v.size
+        if share is not None and v.nbytes > share:
+            keep = share // v.itemsize
+            idx = np.sort(np.random.RandomState(0).choice(total, keep, replace=False))
+            v = v.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(v))
+        written[name] = (tuple(v.shape), total)
+    return written
 
 
 def kernel_roofline(k, events, math_, traffic_json, extra=None):
@@ -188,8 +228,16 @@ def parse():
     ap.add_argument("--poses", type=int, default=100)
     ap.add_argument("--n-samples", type=int, default=None)
     ap.add_argument("--n-importance", type=int, default=None)
+    ap.add_argument("--full", action="store_true",
+                    help="also what takes runs of its own after the timed steps: the "
+                         "serialised per-kernel rooflines, the exact-fp32 leg and the CPU "
+                         "baselines (a plain run leaves those fields null)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (render results, loss, "
+                         "updated parameters) as DIR/<name>.npy, float32, at most "
+                         f"{DUMP_LIMIT_BYTES // 10**6} MB in all")
     ap.add_argument("--cpu-baseline-seconds", type=float, default=12.0,
-                    help="budget of the CPU oracle sample (0 disables)")
+                    help="--full: budget of the CPU oracle sample (0 disables)")
     ap.add_argument("--no-kernel-timing", action="store_true")
     ap.add_argument("--light-shard", action="store_true",
                     help="cfg5 with N>1: render the light image sharded over the ranks and "
@@ -203,7 +251,7 @@ def parse():
                          "{0, 8, 16, 32} per step, train_efficient_sm.py:153-154, drawn from a "
                          "generator seeded alike on every rank)")
     ap.add_argument("--fp32-leg-steps", type=int, default=None,
-                    help="after the timed region, time this many steps (after --warmup "
+                    help="--full: after the timed region, time this many steps (after --warmup "
                          "untimed ones) with the exact fp32 MLP arithmetic "
                          "(v_mfma_f32_32x32x2_f32) for the fp32-MFMA roofline; default: "
                          "--steps; 0 disables")
@@ -248,6 +296,8 @@ def parse():
         a.fp32_leg_steps = a.steps
     if a.chunk <= 0:
         ap.error("--chunk must be positive")
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     dflt = {"cfg5": (1.0, 0.0), "eval": (0.0, 0.0)}.get(a.config, (1.0, 1.0))
     a.perturb = dflt[0] if a.perturb is None else a.perturb
     a.noise_std = dflt[1] if a.noise_std is None else a.noise_std
@@ -546,9 +596,13 @@ def wl_nerf_train(args, dev, rank, ndc):
     S, I = args.n_samples, args.n_importance
     loss_fn = MSELoss()                       # losses.py:4-14 (train.py:107), one launch each way
 
+    last = {}                                 # --dump-outputs: the step that has "on" set
+
     def step():
         rays, rgbs = sampler.next(args.batch)
         res = render_chunked(render_rays, models, emb, rays, args, S, I)
+        if last.get("on"):
+            last["res"] = dict(res)
         return loss_fn(res, rgbs)
 
     hp = hyper(args)
@@ -577,7 +631,7 @@ def wl_nerf_train(args, dev, rank, ndc):
         return cpu_train(args, budget, rays_all, name)
 
     return dict(name=name, metric=metric, workload=work, data=data, step=step, train=True,
-                pipeline_ok=I > 0, models=models, rays_per_step=args.batch, samples_per_ray=S + I,
+                last=last, pipeline_ok=I > 0, models=models, rays_per_step=args.batch, samples_per_ray=S + I,
                 flop_per_ray=S * FLOP_TRAIN + (S + I) * FLOP_TRAIN, cpu=cpu)
 
 
@@ -594,14 +648,20 @@ def wl_eval(args, dev, rank):
     views = [generate_rays(poses[k:k + 1], W, W, blender_focal(W), 1.0, 200.0)
              for k in range(poses.shape[0])]
     it = [rank]
+    last = {}                                 # --dump-outputs: the step that has "on" set
 
     def step():
         rays = views[it[0] % len(views)]
         it[0] += 1
+        parts = [] if last.get("on") else None
         with torch.no_grad():
             for i in range(0, rays.shape[0], args.batch):
-                render_chunked(render_rays, models, emb, rays[i:i + args.batch], args, S, I,
-                               True)
+                res = render_chunked(render_rays, models, emb, rays[i:i + args.batch], args, S, I,
+                                     True)
+                if parts is not None:
+                    parts.append(res)
+        if parts is not None:                 # the view's chunks (concatenated when written)
+            last["res"] = parts
         return None
 
     def cpu(budget):
@@ -613,7 +673,7 @@ def wl_eval(args, dev, rank):
                          f"({W * W} rays, test_time=True: sigma-only coarse {S}, full fine "
                          f"{S + I}; {hyper(args)}, chunks of {args.batch} rays)",
                 data="synthetic (Blender-lego camera orbit, seeded default-init NeRF coarse+fine)",
-                step=step, train=False, models=models, rays_per_step=W * W,
+                step=step, train=False, last=last, models=models, rays_per_step=W * W,
                 samples_per_ray=S + I, flop_per_ray=S * FLOP_FWD_SIGMA + (S + I) * FLOP_FWD,
                 cpu=cpu)
 
@@ -671,6 +731,7 @@ def wl_shadow(args, dev, rank):
     # light renders the same shape (the sharded render gathers them)
     li_rng = np.random.RandomState(2024)
     shard = args.light_shard and dist.is_initialized() and dist.get_world_size() > 1
+    last = {}                                 # --dump-outputs: the step that has "on" set
 
     def step():
         # dataset order (shuffle=False): B consecutive pixels of one view
@@ -695,6 +756,8 @@ def wl_shadow(args, dev, rank):
         tgt = tgt_pool[sel]
         with torch.no_grad():                 # log['train/train_opactiy'] (:191-195)
             opacity_fn(light, tgt)
+        if last.get("on"):
+            last["res"] = dict(out, **{f"light_{k}": v for k, v in light.items()})
         return loss_fn(out, tgt)
 
     lname = "random {0,8,16,32}" if LI == -1 else str(LI)
@@ -716,7 +779,7 @@ def wl_shadow(args, dev, rank):
                          f"{args.lr:g}",
                 data=f"synthetic ({args.poses}-pose camera orbit + one light camera, rays "
                      "generated on device, random targets, seeded default-init NeRF pair)",
-                step=step, train=True, models=models, rays_per_step=B,
+                step=step, train=True, last=last, models=models, rays_per_step=B,
                 samples_per_ray=S + I,
                 flop_per_ray=(S + (S + I)) * FLOP_TRAIN_SIGMA
                 + hw / B * light_samples * (FLOP_TRAIN_SIGMA if gol else FLOP_FWD_SIGMA),
@@ -843,9 +906,10 @@ def main():
         first[0] = False
         return loss
 
-    def run(steps, warmup, what="main"):
+    def run(steps, warmup, what="main", keep_last=False):
         """warmup untimed steps, then `steps` timed ones between barriers;
-        (seconds = max over ranks, last loss)."""
+        (seconds = max over ranks, last loss).  keep_last: the last timed step
+        keeps its render results (wl["last"]["res"], --dump-outputs)."""
         loss = None
         for i in range(warmup):
             step()
@@ -868,8 +932,11 @@ def main():
         timer.ref.record()
         timer.enabled = True
         t0 = time.perf_counter()
-        for _ in range(steps):
+        for _ in range(steps - 1):
             loss = step()
+        wl["last"]["on"] = keep_last
+        loss = step()
+        wl["last"]["on"] = False
         if pstep is not None:
             pstep.flush()        # the last step's deferred fine update is part of it
         if use_dist:
@@ -948,7 +1015,20 @@ def main():
                              **{fp32_key: round(tf_ / FP32_MFMA_PEAK_TF, 4)})
         return ks, roof, roofs, stage
 
-    el, loss = run(args.steps, args.warmup)
+    el, loss = run(args.steps, args.warmup, keep_last=bool(args.dump_outputs))
+    if args.dump_outputs and rank == 0:
+        # before anything below takes further steps: the last timed step's render
+        # results, its loss and the parameters after its optimizer step
+        res = wl["last"].pop("res")
+        if isinstance(res, list):
+            res = {k: torch.cat([p[k] for p in res], 0) for k in res[0]}
+        arrays = {k: v for k, v in res.items() if torch.is_tensor(v)}
+        if loss is not None:
+            arrays["loss"] = loss.reshape(1)
+        if wl["train"]:
+            for tag, m in zip(("coarse", "fine"), wl["models"]):
+                arrays[f"params_{tag}"] = torch.cat([p.detach().reshape(-1) for p in m.parameters()])
+        dump_outputs(args.dump_outputs, arrays)
     ms = el / args.steps * 1e3
     rays_per_s = wl["rays_per_step"] * world * args.steps / el
     math_main = _math()
@@ -977,7 +1057,7 @@ def main():
     # stream gives each kernel's own launch time ("rooflines")
     roofs_conc, roofs_iso = roofs, None
     from nerf_pl_amd import rendering as _rendering
-    if wl["train"] and ks and _rendering.FINE_STREAM:
+    if args.full and wl["train"] and ks and _rendering.FINE_STREAM:
         _rendering.FINE_STREAM = False
         try:
             el_i, _ = run(10, 3, "serialised kernels")
@@ -1000,7 +1080,7 @@ def main():
     # products, no operand splitting) -- its own roofline against the fp32
     # MFMA peak, next to the default arithmetic's
     fp32_leg = None
-    if args.fp32_leg_steps > 0 and math_main != "fp32":
+    if args.full and args.fp32_leg_steps > 0 and math_main != "fp32":
         from nerf_pl_amd import ops as _ops
         _ops.MATH = "fp32"
         try:
@@ -1020,7 +1100,7 @@ def main():
     cpu = None
     cpu1 = None
     progress("done")
-    if rank == 0 and world == 1 and args.cpu_baseline_seconds > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_baseline_seconds > 0:
         cpu = wl["cpu"](args.cpu_baseline_seconds)
         # "... and a 1-thread row too" (a third of the budget)
         global _CPU_THREADS
@@ -1039,6 +1119,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": round(ms, 3),
             "higher_is_better": True,
             "scaling": args.scaling,

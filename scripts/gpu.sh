@@ -41,7 +41,7 @@ run() {  # run <name> <timeout> <cmd...>: stdout to <name>.log, stops the call o
 }
 json() { grep -h '^{' "$out/$1.log" > "$out/$1.json"; }
 # a short bench run to profile: both arithmetics (main region f16x3, the exact-fp32 leg)
-B="bench.py --steps 3 --warmup 2 --fp32-leg-steps 3 --cpu-baseline-seconds 0 --no-kernel-timing ${BENCH_ARGS:-}"
+B="bench.py --full --steps 3 --warmup 2 --fp32-leg-steps 3 --cpu-baseline-seconds 0 --no-kernel-timing ${BENCH_ARGS:-}"
 TR="python -m torch.distributed.run --nnodes=1 --master-addr 127.0.0.1"
 
 for step in "$@"; do
@@ -52,15 +52,15 @@ for step in "$@"; do
   smoke)
     run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
   bench)
-    run bench 400 python bench.py ${BENCH_ARGS:-}; json bench ;;
+    run bench 400 python bench.py --full ${BENCH_ARGS:-}; json bench ;;
   benches)
     for c in cfg3 cfg4 cfg5 cfg5gol eval; do
       a="--config $c"; [ $c = cfg5gol ] && a="--config cfg5 --grad-on-light"
-      run bench_$c 300 python bench.py $a --cpu-baseline-seconds 0; json bench_$c
+      run bench_$c 300 python bench.py --full $a --cpu-baseline-seconds 0; json bench_$c
     done ;;
   stats)
     run stats 300 rocprofv3 --kernel-trace --stats -d "$out/stats" -o run --output-format csv -- \
-      python bench.py --steps 10 --warmup 3 --cpu-baseline-seconds 0 --no-kernel-timing ${BENCH_ARGS:-} ;;
+      python bench.py --full --steps 10 --warmup 3 --cpu-baseline-seconds 0 --no-kernel-timing ${BENCH_ARGS:-} ;;
   sq)
     run sq_a 180 rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY \
       SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_MFMA SQ_INSTS_VALU \
@@ -82,18 +82,18 @@ for step in "$@"; do
           env:*) envs=("${v#env:}") ;;
         esac
         name=ab_$(echo "$v" | tr ':=/' '___')_$i
-        run "$name" 200 env "${envs[@]}" python bench.py --fp32-leg-steps 0 --cpu-baseline-seconds 0 ${BENCH_ARGS:-}
+        run "$name" 200 env "${envs[@]}" python bench.py --full --fp32-leg-steps 0 --cpu-baseline-seconds 0 ${BENCH_ARGS:-}
         grep -h '^{' "$out/$name.log" | python -c 'import json,sys; j=json.loads(sys.stdin.read()); r=j["rooflines"]; f=j.get("fp32_leg") or {}; print(j["value"], j["ms_per_step"], *[(k, r[k]["avg_launch_ms"]) for k in r], "| fp32 leg", f.get("value"), *[(k, v["avg_launch_ms"]) for k, v in (f.get("rooflines") or {}).items()])' || true
       done
     done ;;
   dist)
     NR_BENCH_DIST_BACKEND=gloo run cfg4_gloo4 500 $TR --nproc-per-node 4 --master-port 29621 \
-      bench.py --gpus 4 --config cfg4
-    NR_BENCH_DIST_BACKEND=gloo run cfg2_gloo2 300 $TR --nproc-per-node 2 --master-port 29622 bench.py --gpus 2
+      bench.py --full --gpus 4 --config cfg4
+    NR_BENCH_DIST_BACKEND=gloo run cfg2_gloo2 300 $TR --nproc-per-node 2 --master-port 29622 bench.py --full --gpus 2
     NR_BENCH_DIST_BACKEND=gloo run cfg5_gol_shard_gloo4 500 $TR --nproc-per-node 4 --master-port 29623 \
-      bench.py --gpus 4 --config cfg5 --grad-on-light --light-shard --light-importance -1
+      bench.py --full --gpus 4 --config cfg5 --grad-on-light --light-shard --light-importance -1
     NR_BENCH_FORCE_DIST=1 run cfg2_rccl1 300 $TR --nproc-per-node 1 --master-port 29624 \
-      bench.py --cpu-baseline-seconds 0 ;;
+      bench.py --full --cpu-baseline-seconds 0 ;;
   gaps:*)
     a=${step#gaps:}; a=${a//_/ }
     n=gaps_$(ls -d "$out"/gaps_* 2>/dev/null | wc -l)

@@ -4,6 +4,7 @@ Run in the survey/build container only (it needs /root/reference, which never
 exists on the GPU box):
 
     python tests/golden/make_golden.py
+    python tests/golden/make_golden.py --live     # only tests/golden/live/ (test_oracle_live.py)
 
 What it does
 * imports ``models.nerf`` and ``models.rendering`` from /root/reference.  The
@@ -83,7 +84,7 @@ PROBE_PER_TENSOR = 512
 
 def run_case(ref_nerf, ref_rendering, name, rays, N_samples, N_importance, perturb, noise_std,
              use_disp=False, white_back=False, test_time=False, chunk=32768, sigma_bias=0.0,
-             grads=False, seed=1234):
+             grads=False, seed=1234, out_dir=None):
     torch.manual_seed(seed)
     models = []
     params_seeds = [11, 22]
@@ -170,7 +171,7 @@ def run_case(ref_nerf, ref_rendering, name, rays, N_samples, N_importance, pertu
                     idx = np.sort(pg.choice(flat.size, PROBE_PER_TENSOR, replace=False))
                     out[key + "_idx"] = idx.astype(np.int64)
                     out[key + "_val"] = flat[idx]
-    path = os.path.join(HERE, f"{name}.npz")
+    path = os.path.join(out_dir or HERE, f"{name}.npz")
     np.savez_compressed(path, **out)
     print(f"{name}: {len(rec.draws)} draws, keys={len(out)}, "
           f"{os.path.getsize(path) / 1024:.1f} KiB")
@@ -182,9 +183,38 @@ def pick(rays, n, seed):
     return rays[idx].contiguous()
 
 
+# the cases of tests/test_oracle_live.py: run there against the reference live
+# where a checkout of it exists, and stored once (``--live``) under
+# tests/golden/live/ for every other host
+LIVE = os.path.join(HERE, "live")
+LIVE_CASES = [
+    dict(name="live_cfg2", n=24, seed=21, near=2.0, far=6.0, N_samples=64, N_importance=128,
+         perturb=1.0, noise_std=1.0, sigma_bias=0.5),
+    dict(name="live_cfg1", n=32, seed=22, near=1.0, far=200.0, N_samples=32, N_importance=0,
+         perturb=1.0, noise_std=1.0),
+    dict(name="live_testtime", n=16, seed=23, near=2.0, far=6.0, N_samples=64,
+         N_importance=64, perturb=0.0, noise_std=0.0, test_time=True),
+]
+
+
+def run_live_case(ref, case, out_dir):
+    """one of LIVE_CASES through the reference (``ref`` = import_reference()),
+    its fixture written to ``out_dir``"""
+    c = dict(case)
+    n, seed, near, far = c.pop("n"), c.pop("seed"), c.pop("near"), c.pop("far")
+    rays = pick(blender_rays(64, 2, near=near, far=far), n, seed)
+    torch.manual_seed(0)
+    run_case(*ref, rays=rays, out_dir=out_dir, **c)
+
+
 def main():
     torch.set_num_threads(min(8, os.cpu_count() or 1))
     ref_nerf, ref_rendering = import_reference()
+    if "--live" in sys.argv[1:]:
+        os.makedirs(LIVE, exist_ok=True)
+        for c in LIVE_CASES:
+            run_live_case((ref_nerf, ref_rendering), c, LIVE)
+        return
     lego64_n26 = blender_rays(64, 2, near=2.0, far=6.0)
     lego64_1200 = blender_rays(64, 2, near=1.0, far=200.0)
     fern = llff_ndc_rays(504, 378, n_poses=1)

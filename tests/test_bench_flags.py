@@ -55,6 +55,51 @@ def test_flags_reach_render_rays(monkeypatch):
     assert "perturb=0, noise_std=0, use_disp, white_back, chunk=3" == bench.hyper(a)
 
 
+def test_full_and_dump_outputs_are_off_by_default(monkeypatch):
+    a = _parse(monkeypatch, "--gpus", "1", "--steps", "7", "--warmup", "2")
+    assert a.full is False and a.dump_outputs is None and (a.steps, a.warmup) == (7, 2)
+    a = _parse(monkeypatch, "--full", "--dump-outputs", "some/dir")
+    assert a.full is True and a.dump_outputs == "some/dir"
+    with pytest.raises(SystemExit):           # zero timed steps have no ms_per_step
+        _parse(monkeypatch, "--steps", "0")
+
+
+def test_dump_outputs_writes_every_array_as_float32_npy(tmp_path):
+    import bench
+    import numpy as np
+    g = torch.Generator().manual_seed(3)
+    arrays = {"rgb_fine": torch.rand(37, 3, generator=g).requires_grad_(True),
+              "depth_fine": torch.rand(37, generator=g).double(),
+              "count": torch.arange(5), "loss": torch.rand((), generator=g).reshape(1)}
+    out = tmp_path / "made" / "here"          # created when missing
+    written = bench.dump_outputs(str(out), arrays)
+    assert sorted(p.name for p in out.iterdir()) == sorted(k + ".npy" for k in arrays)
+    for k, t in arrays.items():
+        v = np.load(out / (k + ".npy"), allow_pickle=False)
+        assert v.dtype == (np.float64 if t.dtype == torch.float64 else np.float32)
+        assert v.shape == tuple(t.shape) and written[k] == (tuple(t.shape), t.numel())
+        np.testing.assert_array_equal(v, t.detach().numpy().astype(v.dtype))
+
+
+def test_dump_outputs_keeps_to_its_limit_with_a_fixed_sample(tmp_path):
+    """over the limit, an array larger than an equal share of it is cut to the
+    same seeded sample of its elements in every run; smaller ones stay whole"""
+    import bench
+    import numpy as np
+    big = torch.arange(1000, dtype=torch.float32).reshape(250, 4)
+    small = torch.arange(10, dtype=torch.float32)
+    for d in ("a", "b"):
+        w = bench.dump_outputs(str(tmp_path / d), {"big": big, "small": small}, limit_bytes=800)
+        assert w == {"big": ((100,), 1000), "small": ((10,), 10)}
+    a, b = (np.load(tmp_path / d / "big.npy") for d in ("a", "b"))
+    np.testing.assert_array_equal(a, b)
+    assert (np.diff(a) > 0).all() and a.min() >= 0 and a.max() < 1000   # distinct elements of big
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "small.npy"), small.numpy())
+    total = sum(os.path.getsize(tmp_path / "a" / f) - 128 for f in ("big.npy", "small.npy"))
+    assert total <= 800
+    assert bench.DUMP_LIMIT_BYTES <= 64 * 10**6
+
+
 def test_one_call_when_the_batch_fits_a_chunk(monkeypatch):
     import bench
     a = _parse(monkeypatch)
