@@ -336,6 +336,29 @@ int nr_composite_bwd(const float* raw, int raw_stride, int sig_col, const float*
                      int n_samples, int white_back, const float* g_rgb, const float* g_depth,
                      const float* g_opacity, float* g_raw, void* stream);
 
+/* The compositing of models/rendering_rgb_sm.py (:181-202): nr_composite_fwd
+ * plus disp (n_rays) = 1 / max(1e-10, depth / opacity) (:197), formed in fp32
+ * from the depth and opacity it stores, NaN where opacity == 0 (torch.max
+ * propagates the 0 / 0).  Every other output carries nr_composite_fwd's bits;
+ * white_back does not enter disp; weights_only writes no disp (may be NULL). */
+int nr_composite_disp_fwd(const float* raw, int raw_stride, int sig_col, const float* z,
+                          const float* rays, const float* noise, float noise_std, uint64_t seed,
+                          int rng_stream, int64_t n_rays, int n_samples, int white_back,
+                          int weights_only, float* rgb, float* depth, float* opacity,
+                          float* disp, float* weights, void* stream);
+
+/* nr_composite_bwd plus g_disp (n_rays): with depth and opacity the forward's
+ * outputs D and O, a ray with D / O > 1e-10 adds g_disp * (-O / D^2) to its
+ * depth gradient and g_disp / D to its opacity gradient (evaluated per sample
+ * as g_disp (D - O z_i) / D^2, which does not cancel); a clamped ray adds
+ * exactly 0.  g_disp == NULL (depth, opacity then unread): nr_composite_bwd. */
+int nr_composite_disp_bwd(const float* raw, int raw_stride, int sig_col, const float* z,
+                          const float* rays, const float* noise, float noise_std, uint64_t seed,
+                          int rng_stream, int64_t n_rays, int n_samples, int white_back,
+                          const float* g_rgb, const float* g_depth, const float* g_opacity,
+                          const float* g_disp, const float* depth, const float* opacity,
+                          float* g_raw, void* stream);
+
 /* sample_pdf (rendering.py:14-48) replacing torchsearchsorted.searchsorted
  * (side='right', rendering.py:37), fused with sort(cat[z_coarse, z_pdf])
  * (rendering.py:257).  weights: coarse weights (n_rays, n_samples), bins are

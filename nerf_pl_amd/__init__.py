@@ -18,10 +18,11 @@ if (_os.environ.get("NERF_PL_AMD_KEEP_HW_QUEUES") != "1"
     _os.environ["GPU_MAX_HW_QUEUES"] = "8"
 
 from .nerf import Embedding, NeRF  # noqa: E402
+from . import rendering_rgb_sm  # noqa: E402
 from .rendering import render_rays, sample_pdf  # noqa: E402
 from .rng import PhiloxRNG, ReplayRNG  # noqa: E402
 from .searchsorted import searchsorted  # noqa: E402
 
 __all__ = ["Embedding", "NeRF", "render_rays", "sample_pdf", "searchsorted", "PhiloxRNG",
-           "ReplayRNG"]
+           "ReplayRNG", "rendering_rgb_sm"]
 __version__ = "0.1.0"

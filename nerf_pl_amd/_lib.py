@@ -92,6 +92,10 @@ SIGNATURES = {
                          _p, _p],
     "nr_composite_bwd": [_p, _i, _i, _p, _p, _p, _f, _u64, _i, _i64, _i, _i, _p, _p, _p, _p,
                          _p],
+    "nr_composite_disp_fwd": [_p, _i, _i, _p, _p, _p, _f, _u64, _i, _i64, _i, _i, _i, _p, _p, _p,
+                              _p, _p, _p],
+    "nr_composite_disp_bwd": [_p, _i, _i, _p, _p, _p, _f, _u64, _i, _i64, _i, _i, _p, _p, _p, _p,
+                              _p, _p, _p, _p],
     "nr_gen_rays": [_p, _i64, _i, _i, _f, _f, _f, _f, _f, _i, _f, _f, _f, _f, _p, _i64, _p, _p,
                     _p, _p],
     "nr_adam_max_tensors": [],

@@ -79,6 +79,7 @@ struct CompArgs {
     float noise_std; uint64_t seed; uint32_t stream;
     int n_rays, S, white_back, weights_only;
     float* rgb; float* depth; float* opacity; float* weights;
+    float* disp;   // (n_rays) or null: nr_composite_disp_fwd (rendering_rgb_sm.py:197)
 };
 
 __device__ __forceinline__ float ray_dnorm(const float* r) {
@@ -106,6 +107,8 @@ __device__ __forceinline__ float alpha_of(float sigma, float noise, float delta)
     return 1.f - expf(nr_mul(-delta, r));
 }
 
+// DISP: the entry point with the disparity map (a.disp != null)
+template <bool DISP>
 __global__ void composite_fwd_kernel(CompArgs a) {
     const int lane = threadIdx.x & 63;
     const int ray = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
@@ -171,8 +174,17 @@ __global__ void composite_fwd_kernel(CompArgs a) {
             a.rgb[(size_t)ray * 3 + 1] = acc_g + bg;
             a.rgb[(size_t)ray * 3 + 2] = acc_b + bg;
         }
-        a.depth[ray] = (float)acc_d;
+        const float depth = (float)acc_d;
+        a.depth[ray] = depth;
         a.opacity[ray] = acc_w;
+        if (DISP) {
+            // 1 / torch.max(1e-10, depth / opacity) (rendering_rgb_sm.py:197), from
+            // the two fp32 values just stored; white_back does not enter.
+            // torch.max propagates NaN (0 / 0 on a ray of zero opacity) where
+            // fmaxf would return the clamp
+            const float q = depth / acc_w;
+            a.disp[ray] = 1.f / ((q > 1e-10f || q != q) ? q : 1e-10f);
+        }
     }
 }
 
@@ -197,6 +209,9 @@ struct CompBwdArgs {
     int n_rays, S, white_back;
     const float* g_rgb; const float* g_depth; const float* g_opacity;
     float* g_raw;   // (n_rays*S, raw_stride)
+    // nr_composite_disp_bwd: d loss / d disp and the forward's depth and opacity
+    // (null from nr_composite_bwd)
+    const float* g_disp; const float* depth; const float* opacity;
 };
 
 // delta_i in double from the fp32 depths (the last: 1e10 |d|, rendering.py:171)
@@ -205,6 +220,8 @@ __device__ __forceinline__ double delta_d(const float* z, int64_t base, int i, i
     return S > 1 ? 1e10 * dn : 0.0;
 }
 
+// DISP: a.g_disp != null
+template <bool DISP>
 __global__ void composite_bwd_kernel(CompBwdArgs a) {
     const int lane = threadIdx.x & 63;
     const int ray = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
@@ -218,6 +235,23 @@ __global__ void composite_bwd_kernel(CompBwdArgs a) {
     const float gb = a.g_rgb ? a.g_rgb[(size_t)ray * 3 + 2] : 0.f;
     const float gd = a.g_depth ? a.g_depth[ray] : 0.f;
     double go = a.g_opacity ? a.g_opacity[ray] : 0.f;
+    // disp = O / D where q = D / O > 1e-10 (the forward's fp32 quotient, D and
+    // O its stored outputs), constant in the clamped branch: g_disp adds
+    // g_disp * (-O / D^2) to the depth gradient and g_disp / D to the opacity
+    // gradient, i.e. gq (D - O z_i) to dw_i with gq = g_disp / D^2.  Kept as
+    // that one difference (O z_i is exact in double): on a ray whose weight
+    // sits on one sample D = O z_i and the two folded terms would cancel to
+    // rounding noise where the gradient is exactly 0
+    bool has_q = false;
+    double gq = 0.0, Dq = 0.0, Oq = 0.0;
+    if (DISP) {
+        const float D = a.depth[ray], O = a.opacity[ray];
+        if (D / O > 1e-10f) {
+            has_q = true;
+            Dq = D; Oq = O;
+            gq = (double)a.g_disp[ray] / (Dq * Dq);
+        }
+    }
     if (a.white_back) go -= (double)gr + (double)gg + (double)gb;
     const int nchunks = (S + 63) >> 6;
     // relu(sigma + noise) as the forward forms it (fp32 add), widened
@@ -262,7 +296,10 @@ __global__ void composite_bwd_kernel(CompBwdArgs a) {
         if (lane == 0) excl = 1.0;
         const double T = carry * excl;
         double dw = 0.0;
-        if (v) dw = (double)gr * cr + (double)gg * cg + (double)gb * cb + (double)gd * zi + go;
+        if (v) {
+            dw = (double)gr * cr + (double)gg * cg + (double)gb * cb + (double)gd * zi + go;
+            if (has_q) dw += gq * (Dq - Oq * (double)zi);
+        }
         // suffix affine scan inside the chunk: element i contributes the map
         // R -> f_i R + dw_i a_i to the samples before it.
         double A = fac, Bv = v ? dw * alpha : 0.0;
@@ -431,25 +468,77 @@ NR_API int nr_coarse_z(const float* rays, const float* tlin, int64_t n_rays, int
     return 0;
 }
 
+namespace {
+
+int composite_fwd(const char* who, const float* raw, int raw_stride, int sig_col, const float* z,
+                  const float* rays, const float* noise, float noise_std, uint64_t seed,
+                  int rng_stream, int64_t n_rays, int n_samples, int white_back, int weights_only,
+                  float* rgb, float* depth, float* opacity, float* weights, float* disp,
+                  void* stream) {
+    NR_REQUIRE(n_rays >= 0 && n_samples > 0, "%s: bad sizes", who);
+    if (n_rays == 0) return 0;
+    NR_REQUIRE(raw && z && rays && opacity && weights, "%s: null pointer", who);
+    NR_REQUIRE(weights_only || depth, "%s: null depth", who);
+    NR_REQUIRE(sig_col >= 0 && sig_col < raw_stride && (!rgb || raw_stride >= 4),
+               "%s: bad raw layout (stride %d, sigma column %d)", who, raw_stride, sig_col);
+    CompArgs a{raw, raw_stride, sig_col, z, rays, noise, noise_std, seed, (uint32_t)rng_stream,
+               (int)n_rays, n_samples, white_back, weights_only, rgb, depth, opacity, weights,
+               disp};
+    const int wpb = 4;
+    const dim3 grid((unsigned)((n_rays + wpb - 1) / wpb)), block(64 * wpb);
+    if (disp) composite_fwd_kernel<true><<<grid, block, 0, (hipStream_t)stream>>>(a);
+    else composite_fwd_kernel<false><<<grid, block, 0, (hipStream_t)stream>>>(a);
+    NR_LAUNCH_CHECK(who);
+    return 0;
+}
+
+int composite_bwd(const char* who, const float* raw, int raw_stride, int sig_col, const float* z,
+                  const float* rays, const float* noise, float noise_std, uint64_t seed,
+                  int rng_stream, int64_t n_rays, int n_samples, int white_back,
+                  const float* g_rgb, const float* g_depth, const float* g_opacity,
+                  const float* g_disp, const float* depth, const float* opacity, float* g_raw,
+                  void* stream) {
+    NR_REQUIRE(n_rays >= 0 && n_samples > 0, "%s: bad sizes", who);
+    if (n_rays == 0) return 0;
+    NR_REQUIRE(raw && z && rays && g_raw, "%s: null pointer", who);
+    NR_REQUIRE(!g_disp || (depth && opacity), "%s: g_disp needs the forward's depth and opacity",
+               who);
+    NR_REQUIRE(raw_stride == 4 ? sig_col == 3 : (raw_stride == 1 && sig_col == 0),
+               "%s: raw rows must be [rgb, sigma] or [sigma]", who);
+    NR_REQUIRE(raw_stride != 4 || ((uintptr_t)g_raw & 15) == 0,
+               "%s: g_raw must be 16-byte aligned", who);
+    CompBwdArgs a{raw, raw_stride, sig_col, z, rays, noise, noise_std, seed, (uint32_t)rng_stream,
+                  (int)n_rays, n_samples, white_back, g_rgb, g_depth, g_opacity, g_raw,
+                  g_disp, depth, opacity};
+    const int wpb = 4;
+    const dim3 grid((unsigned)((n_rays + wpb - 1) / wpb)), block(64 * wpb);
+    if (g_disp) composite_bwd_kernel<true><<<grid, block, 0, (hipStream_t)stream>>>(a);
+    else composite_bwd_kernel<false><<<grid, block, 0, (hipStream_t)stream>>>(a);
+    NR_LAUNCH_CHECK(who);
+    return 0;
+}
+
+}  // namespace
+
 NR_API int nr_composite_fwd(const float* raw, int raw_stride, int sig_col, const float* z,
                             const float* rays, const float* noise, float noise_std, uint64_t seed,
                             int rng_stream, int64_t n_rays, int n_samples, int white_back,
                             int weights_only, float* rgb, float* depth, float* opacity,
                             float* weights, void* stream) {
-    NR_REQUIRE(n_rays >= 0 && n_samples > 0, "nr_composite_fwd: bad sizes");
-    if (n_rays == 0) return 0;
-    NR_REQUIRE(raw && z && rays && opacity && weights, "nr_composite_fwd: null pointer");
-    NR_REQUIRE(weights_only || depth, "nr_composite_fwd: null depth");
-    NR_REQUIRE(sig_col >= 0 && sig_col < raw_stride && (!rgb || raw_stride >= 4),
-               "nr_composite_fwd: bad raw layout (stride %d, sigma column %d)", raw_stride,
-               sig_col);
-    CompArgs a{raw, raw_stride, sig_col, z, rays, noise, noise_std, seed, (uint32_t)rng_stream,
-               (int)n_rays, n_samples, white_back, weights_only, rgb, depth, opacity, weights};
-    const int wpb = 4;
-    composite_fwd_kernel<<<(unsigned)((n_rays + wpb - 1) / wpb), 64 * wpb, 0,
-                           (hipStream_t)stream>>>(a);
-    NR_LAUNCH_CHECK("nr_composite_fwd");
-    return 0;
+    return composite_fwd("nr_composite_fwd", raw, raw_stride, sig_col, z, rays, noise, noise_std,
+                         seed, rng_stream, n_rays, n_samples, white_back, weights_only, rgb, depth,
+                         opacity, weights, nullptr, stream);
+}
+
+NR_API int nr_composite_disp_fwd(const float* raw, int raw_stride, int sig_col, const float* z,
+                                 const float* rays, const float* noise, float noise_std,
+                                 uint64_t seed, int rng_stream, int64_t n_rays, int n_samples,
+                                 int white_back, int weights_only, float* rgb, float* depth,
+                                 float* opacity, float* disp, float* weights, void* stream) {
+    NR_REQUIRE(n_rays <= 0 || weights_only || disp, "nr_composite_disp_fwd: null disp");
+    return composite_fwd("nr_composite_disp_fwd", raw, raw_stride, sig_col, z, rays, noise,
+                         noise_std, seed, rng_stream, n_rays, n_samples, white_back, weights_only,
+                         rgb, depth, opacity, weights, weights_only ? nullptr : disp, stream);
 }
 
 NR_API int nr_composite_bwd(const float* raw, int raw_stride, int sig_col, const float* z,
@@ -458,20 +547,20 @@ NR_API int nr_composite_bwd(const float* raw, int raw_stride, int sig_col, const
                             int64_t n_rays, int n_samples, int white_back, const float* g_rgb,
                             const float* g_depth, const float* g_opacity, float* g_raw,
                             void* stream) {
-    NR_REQUIRE(n_rays >= 0 && n_samples > 0, "nr_composite_bwd: bad sizes");
-    if (n_rays == 0) return 0;
-    NR_REQUIRE(raw && z && rays && g_raw, "nr_composite_bwd: null pointer");
-    NR_REQUIRE(raw_stride == 4 ? sig_col == 3 : (raw_stride == 1 && sig_col == 0),
-               "nr_composite_bwd: raw rows must be [rgb, sigma] or [sigma]");
-    NR_REQUIRE(raw_stride != 4 || ((uintptr_t)g_raw & 15) == 0,
-               "nr_composite_bwd: g_raw must be 16-byte aligned");
-    CompBwdArgs a{raw, raw_stride, sig_col, z, rays, noise, noise_std, seed, (uint32_t)rng_stream, (int)n_rays,
-                  n_samples, white_back, g_rgb, g_depth, g_opacity, g_raw};
-    const int wpb = 4;
-    composite_bwd_kernel<<<(unsigned)((n_rays + wpb - 1) / wpb), 64 * wpb, 0,
-                           (hipStream_t)stream>>>(a);
-    NR_LAUNCH_CHECK("nr_composite_bwd");
-    return 0;
+    return composite_bwd("nr_composite_bwd", raw, raw_stride, sig_col, z, rays, noise, noise_std,
+                         seed, rng_stream, n_rays, n_samples, white_back, g_rgb, g_depth,
+                         g_opacity, nullptr, nullptr, nullptr, g_raw, stream);
+}
+
+NR_API int nr_composite_disp_bwd(const float* raw, int raw_stride, int sig_col, const float* z,
+                                 const float* rays, const float* noise, float noise_std,
+                                 uint64_t seed, int rng_stream, int64_t n_rays, int n_samples,
+                                 int white_back, const float* g_rgb, const float* g_depth,
+                                 const float* g_opacity, const float* g_disp, const float* depth,
+                                 const float* opacity, float* g_raw, void* stream) {
+    return composite_bwd("nr_composite_disp_bwd", raw, raw_stride, sig_col, z, rays, noise,
+                         noise_std, seed, rng_stream, n_rays, n_samples, white_back, g_rgb,
+                         g_depth, g_opacity, g_disp, depth, opacity, g_raw, stream);
 }
 
 NR_API int nr_sample_pdf(const float* weights, int n_samples, const float* rays,

@@ -333,3 +333,36 @@ def composite_apply(raw, z, rays, noise, noise_std, seed, stream, white_back):
     if torch.is_grad_enabled() and raw.requires_grad:
         return _Composite.apply(raw, z, rays, noise, noise_std, seed, stream, white_back)
     return ops.composite_forward(raw, z, rays, noise, noise_std, seed, stream, white_back)
+
+
+class _CompositeDisp(torch.autograd.Function):
+    """_Composite with the disparity map of rendering_rgb_sm.py:197
+    (``nr_composite_disp_*``): outputs (rgb, depth, opacity, disp, weights)."""
+
+    @staticmethod
+    def forward(ctx, raw, z, rays, noise, noise_std, seed, stream, white_back):
+        rgb, depth, opac, disp, w = ops.composite_disp_forward(raw, z, rays, noise, noise_std,
+                                                               seed, stream, white_back)
+        ctx.save_for_backward(raw, z, rays, noise if noise is not None else torch.empty(0),
+                              depth, opac)
+        ctx.cfg = (noise is not None, noise_std, seed, stream, white_back)
+        ctx.mark_non_differentiable(w)
+        # as in _Composite; an unused disp (the joint trainer's loss reads rgb
+        # and, through the shadow map, depth) costs the backward nothing
+        ctx.set_materialize_grads(False)
+        return rgb, depth, opac, disp, w
+
+    @staticmethod
+    def backward(ctx, g_rgb, g_depth, g_opac, g_disp, g_w):   # noqa: ARG004
+        raw, z, rays, noise, depth, opac = ctx.saved_tensors
+        has_noise, noise_std, seed, stream, white_back = ctx.cfg
+        g_raw = ops.composite_disp_backward(raw, z, rays, noise if has_noise else None, noise_std,
+                                            seed, stream, white_back, g_rgb, g_depth, g_opac,
+                                            g_disp, depth, opac)
+        return g_raw, None, None, None, None, None, None, None
+
+
+def composite_disp_apply(raw, z, rays, noise, noise_std, seed, stream, white_back):
+    if torch.is_grad_enabled() and raw.requires_grad:
+        return _CompositeDisp.apply(raw, z, rays, noise, noise_std, seed, stream, white_back)
+    return ops.composite_disp_forward(raw, z, rays, noise, noise_std, seed, stream, white_back)

@@ -86,9 +86,15 @@ def _mlp(model, embeddings, xyz, dir_emb, chunk, sigma_only):
     return torch.cat(outs, 0)
 
 
+def _disparity(depth, w):
+    """rendering_rgb_sm.py:197 (torch.max propagates the NaN of a 0 / 0)"""
+    return 1. / torch.max(1e-10 * torch.ones_like(depth), depth / torch.sum(w, -1))
+
+
 def render_rays_host(models, embeddings, rays, N_samples, use_disp, perturb, noise_std,
-                     N_importance, chunk, white_back, test_time, rng, capture=None):
-    """rendering.py:84-272 on host tensors (see the module docstring)"""
+                     N_importance, chunk, white_back, test_time, rng, capture=None, disp=False):
+    """rendering.py:84-272 on host tensors (see the module docstring);
+    ``disp``: rendering_rgb_sm.py:84-277, the same render with ``disp_map_*``"""
     if embeddings is None:
         raise ValueError("nerf_pl_amd.render_rays: a host batch needs its embeddings")
     for m in models:
@@ -121,6 +127,8 @@ def render_rays_host(models, embeddings, rays, N_samples, use_disp, perturb, noi
         result["rgb_coarse"] = rgb_c
         result["depth_coarse"] = depth_c
         result["opacity_coarse"] = w_c.sum(1)
+        if disp:
+            result["disp_map_coarse"] = _disparity(depth_c, w_c)
     cap["weights_coarse"] = w_c
     if N_importance > 0:
         u = rng.rand((n, N_importance), dev)
@@ -138,4 +146,6 @@ def render_rays_host(models, embeddings, rays, N_samples, use_disp, perturb, noi
         result["rgb_fine"] = rgb_f
         result["depth_fine"] = depth_f
         result["opacity_fine"] = w_f.sum(1)
+        if disp:
+            result["disp_map_fine"] = _disparity(depth_f, w_f)
     return result

@@ -286,6 +286,40 @@ def composite_backward(raw, z, rays, noise, noise_std, seed, rng_stream, white_b
     return g_raw
 
 
+def composite_disp_forward(raw, z, rays, noise, noise_std, seed, rng_stream, white_back):
+    """composite_forward plus disp = 1 / max(1e-10, depth / opacity)
+    (rendering_rgb_sm.py:197): (rgb, depth, opacity, disp, weights)."""
+    z = _dev(z, "z")
+    n_rays, S = z.shape
+    stride = raw.shape[-1]
+    dev = z.device
+    opac = torch.empty(n_rays, device=dev)
+    w = torch.empty(n_rays, S, device=dev)
+    rgb = None if stride < 4 else torch.empty(n_rays, 3, device=dev)
+    depth = torch.empty(n_rays, device=dev)
+    disp = torch.empty(n_rays, device=dev)
+    call("nr_composite_disp_fwd", ptr(raw), stride, stride - 1, ptr(z), ptr(rays), ptr(noise),
+         float(noise_std), seed, rng_stream, n_rays, S, int(white_back), 0, ptr(rgb), ptr(depth),
+         ptr(opac), ptr(disp), ptr(w), stream_of(dev))
+    return rgb, depth, opac, disp, w
+
+
+def composite_disp_backward(raw, z, rays, noise, noise_std, seed, rng_stream, white_back,
+                            g_rgb, g_depth, g_opacity, g_disp=None, depth=None, opacity=None):
+    """composite_backward with the disparity's gradient; ``depth`` / ``opacity``
+    are composite_disp_forward's outputs (read only when ``g_disp`` is given)."""
+    n_rays, S = z.shape
+    stride = raw.shape[-1]
+    g_raw = torch.empty(n_rays * S, stride, device=z.device)
+
+    def c(t):
+        return ptr(None if t is None else t.contiguous())
+    call("nr_composite_disp_bwd", ptr(raw), stride, stride - 1, ptr(z), ptr(rays), ptr(noise),
+         float(noise_std), seed, rng_stream, n_rays, S, int(white_back), c(g_rgb), c(g_depth),
+         c(g_opacity), c(g_disp), c(depth), c(opacity), ptr(g_raw), stream_of(z.device))
+    return g_raw
+
+
 def sample_pdf(weights, rays, n_importance, u=None, jitter=None, seed=0, z_coarse=None,
                merge=False):
     """Importance depths (R, I); with merge=True also the sorted (R, S+I) fine depths."""

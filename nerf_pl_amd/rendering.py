@@ -28,7 +28,7 @@ import os
 import torch
 
 from . import ops
-from .functions import composite_apply, mlp_apply
+from .functions import composite_apply, composite_disp_apply, mlp_apply
 from .rng import (STREAM_JITTER, STREAM_NOISE_COARSE, STREAM_NOISE_FINE, STREAM_PERTURB,
                   STREAM_U, PhiloxRNG, TorchRNG)
 
@@ -121,7 +121,19 @@ def sample_pdf(rays, weights, N_importance, det=False, eps=1e-5, *, rng=None):
 def render_rays(models, embeddings, rays, N_samples=64, use_disp=False, perturb=0, noise_std=1,
                 N_importance=0, chunk=1024 * 32, white_back=False, test_time=False, *, rng=None,
                 _capture=None):
+    return _render_rays(models, embeddings, rays, N_samples, use_disp, perturb, noise_std,
+                        N_importance, chunk, white_back, test_time, rng, _capture)
+
+
+def _render_rays(models, embeddings, rays, N_samples, use_disp, perturb, noise_std, N_importance,
+                 chunk, white_back, test_time, rng, _capture, disp=False, depth_only=False):
+    """The render behind ``rendering.render_rays`` and, with ``disp``,
+    ``rendering_rgb_sm.render_rays`` (the same function plus ``disp_map_*``,
+    rendering_rgb_sm.py:197, 253, 276).  ``depth_only``: every MLP call is the
+    sigma-only graph and no ``rgb_*`` is produced."""
     if isinstance(rays, torch.Tensor) and rays.device.type == "cpu":
+        if depth_only:
+            raise NotImplementedError("nerf_pl_amd.render_rays: depth_only needs a HIP-device batch")
         if rays.dtype != torch.float32:
             raise TypeError(f"rays: expected float32, got {rays.dtype}")
         if rays.dim() != 2 or rays.shape[-1] != 8:
@@ -129,7 +141,7 @@ def render_rays(models, embeddings, rays, N_samples=64, use_disp=False, perturb=
         from .host import render_rays_host
         return render_rays_host(models, embeddings, rays, N_samples, use_disp, perturb, noise_std,
                                 N_importance, chunk, white_back, test_time,
-                                TorchRNG() if rng is None else rng, _capture)
+                                TorchRNG() if rng is None else rng, _capture, disp=disp)
     del chunk
     fused = _fused_ok(models, embeddings)
 
@@ -149,6 +161,22 @@ def render_rays(models, embeddings, rays, N_samples=64, use_disp=False, perturb=
     rng = PhiloxRNG() if rng is None else rng
     seed = rng.seed
 
+    def composite(result, level, raw, z, noise, stream):
+        """compositing of one pass into ``result``; returns the weights"""
+        if disp:
+            rgb, depth, opac, dmap, w = composite_disp_apply(raw, z, rays, noise, noise_std, seed,
+                                                             stream, white_back)
+        else:
+            rgb, depth, opac, w = composite_apply(raw, z, rays, noise, noise_std, seed, stream,
+                                                  white_back)
+        if rgb is not None:
+            result["rgb_" + level] = rgb
+        result["depth_" + level] = depth
+        result["opacity_" + level] = opac
+        if disp:
+            result["disp_map_" + level] = dmap
+        return w
+
     # stratified coarse depths (rendering.py:216-232)
     u1 = rng.rand((n_rays, N_samples), dev) if perturb > 0 else None
     z_c = ops.coarse_z(rays, N_samples, use_disp, perturb, u=u1, seed=seed)
@@ -166,12 +194,8 @@ def render_rays(models, embeddings, rays, N_samples=64, use_disp=False, perturb=
                                                       weights_only=True)
         result["opacity_coarse"] = opac_c
     else:
-        raw_c = mlp(models[0], z_c, N_samples)
-        rgb_c, depth_c, opac_c, w_c = composite_apply(raw_c, z_c, rays, noise_c, noise_std, seed,
-                                                      STREAM_NOISE_COARSE, white_back)
-        result["rgb_coarse"] = rgb_c
-        result["depth_coarse"] = depth_c
-        result["opacity_coarse"] = opac_c
+        raw_c = mlp(models[0], z_c, N_samples, sigma_only=depth_only)
+        w_c = composite(result, "coarse", raw_c, z_c, noise_c, STREAM_NOISE_COARSE)
 
     cap["weights_coarse"] = w_c
     if N_importance > 0:
@@ -183,11 +207,13 @@ def render_rays(models, embeddings, rays, N_samples=64, use_disp=False, perturb=
         cap["z_fine"] = z_f
         s_f = N_samples + N_importance
 
+        fine = {}
+
         def fine_pass():
             noise_f = rng.randn((n_rays, s_f), dev)
-            raw_f = mlp(models[1], z_f, s_f)
-            return composite_apply(raw_f, z_f, rays, noise_f, noise_std, seed, STREAM_NOISE_FINE,
-                                   white_back)
+            raw_f = mlp(models[1], z_f, s_f, sigma_only=depth_only)
+            w = composite(fine, "fine", raw_f, z_f, noise_f, STREAM_NOISE_FINE)
+            return tuple(fine.values()) + (w,)
 
         while BEFORE_FINE:
             BEFORE_FINE.pop(0)()
@@ -204,13 +230,10 @@ def render_rays(models, embeddings, rays, N_samples=64, use_disp=False, perturb=
                 t.record_stream(side)
             for t in outs:
                 t.record_stream(main)
-            rgb_f, depth_f, opac_f, w_f = outs
         else:
-            rgb_f, depth_f, opac_f, w_f = fine_pass()
-        cap["weights_fine"] = w_f
-        result["rgb_fine"] = rgb_f
-        result["depth_fine"] = depth_f
-        result["opacity_fine"] = opac_f
+            outs = fine_pass()
+        cap["weights_fine"] = outs[-1]
+        result.update(fine)
     return result
 
 

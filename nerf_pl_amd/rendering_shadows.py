@@ -23,8 +23,9 @@ from __future__ import annotations
 
 import torch
 
+from . import efficient_shadow_mapping as _esm
 from . import ops
-from .efficient_shadow_mapping import EPSILON, _cam, normed_depth, shadow_map
+from .efficient_shadow_mapping import EPSILON, _cam
 from .functions import composite_apply, mlp_apply
 from .rendering import _check_embeddings
 from .rng import STREAM_NOISE_COARSE, STREAM_NOISE_FINE, PhiloxRNG
@@ -133,6 +134,14 @@ def efficient_sm(cam_pixels, light_pixels, cam_results, light_results, ppc, ligh
     (B,3,3)} (collated per ray); ``light_ppc`` a ``Camera`` or the same dict for
     one camera.  Writes ``rgb_coarse`` (and ``rgb_fine``) = shadow + 1e-5 into
     ``cam_results`` and returns it."""
+    return _efficient_sm(cam_pixels, light_pixels, cam_results, light_results, ppc, light_ppc,
+                         image_shape, fine_sampling, Light_N_importance, shadow_method, "rgb")
+
+
+def _efficient_sm(cam_pixels, light_pixels, cam_results, light_results, ppc, light_ppc,
+                  image_shape, fine_sampling, Light_N_importance, shadow_method, out_key):
+    """``efficient_sm`` writing ``<out_key>_coarse`` / ``<out_key>_fine``: "rgb"
+    here, "sm" in rendering_rgb_sm (rendering_rgb_sm.py:458, 477)"""
     d_c = cam_results["depth_coarse"]
     dev = d_c.device
     n = d_c.shape[0]
@@ -143,14 +152,14 @@ def efficient_sm(cam_pixels, light_pixels, cam_results, light_results, ppc, ligh
     cam_pixels = ops.to_device_f32(cam_pixels, dev)
     light_pixels = ops.to_device_f32(light_pixels, dev).reshape(-1, 3)
 
-    light_c = normed_depth(lcam, light_pixels, light_results["depth_coarse"])
-    sm_c = shadow_map(d_c, cam_pixels, eye, cams, leye, lcam, light_c, image_shape,
-                      shadow_method, out_eps=EPSILON)
-    cam_results["rgb_coarse"] = sm_c
+    light_c = _esm.normed_depth(lcam, light_pixels, light_results["depth_coarse"])
+    sm_c = _esm.shadow_map(d_c, cam_pixels, eye, cams, leye, lcam, light_c, image_shape,
+                           shadow_method, out_eps=EPSILON)
+    cam_results[out_key + "_coarse"] = sm_c
     if fine_sampling:
-        light_f = (normed_depth(lcam, light_pixels, light_results["depth_fine"])
+        light_f = (_esm.normed_depth(lcam, light_pixels, light_results["depth_fine"])
                    if Light_N_importance else light_c)
-        cam_results["rgb_fine"] = shadow_map(cam_results["depth_fine"], cam_pixels, eye, cams,
-                                             leye, lcam, light_f, image_shape, shadow_method,
-                                             out_eps=EPSILON)
+        cam_results[out_key + "_fine"] = _esm.shadow_map(
+            cam_results["depth_fine"], cam_pixels, eye, cams, leye, lcam, light_f, image_shape,
+            shadow_method, out_eps=EPSILON)
     return cam_results
