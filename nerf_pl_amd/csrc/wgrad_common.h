@@ -1,0 +1,124 @@
+// Weight gradient (wgrad.hip): what its kernels share -- the task and launch
+// structs, the split-K and fusion constants, the flat parameter offsets.
+#pragma once
+#include "x3.h"
+
+namespace {
+
+constexpr int kTasks = 14;
+constexpr int kTargetWG = 760;   // ~3 rounds of one workgroup per CU (short tail)
+// the gathering kernels (a sample list, gathered inputs): 1024 measured 1.5%
+// faster than 760 at cfg2's fine pass (three alternating rounds, profiles/r04/abalt_tw)
+constexpr int kTargetWGGather = 1024;
+// the LDS-DMA kernel (wgrad4_kernel, one workgroup per CU) over a sample list:
+// 1536 measured 3% faster than 1024 (768: +0.5%, 2048: -1.5%) at cfg2's fine
+// pass (two alternating rounds, profiles/r05/ab/u_*)
+constexpr int kTargetWGW4 = 1536;
+constexpr int kMax2(int x, int y) { return x > y ? x : y; }
+[[maybe_unused]] constexpr int kTargetWGMax = kMax2(kMax2(kTargetWG, kTargetWGGather), kTargetWGW4);
+constexpr int kThreads = 512;    // 8 waves: two per SIMD, so one wave's staging and
+                                 // barrier time overlaps its partner's MFMAs
+
+enum SegKind { SEG_ACC = 0, SEG_PE = 1, SEG_DPE = 2, SEG_HEAD = 3 };
+
+// f16x3: the task pairs that read the same saved segment (wgrad_launch:
+// DZ(4), H(7), dz_dir) run fused -- one workgroup stages the shared segment
+// once and computes both outputs.
+constexpr bool kFuse = NR_F16 || NR_BF1;
+// bit i: pair i of wgrad_launch's kFused (f16x3 6: no spills, measured slower)
+constexpr int kFuseMask = 7;
+// the same for the gathering kernels (the *_active entry points): the fused
+// PE pair (bit 0) leaves wgrad3_kernel<true, ROWS> 33 spilled VGPRs (8
+// without it), and unfused its fine-pass launch runs 1.97 -> 1.83 ms
+// (three alternating same-box rounds, profiles/r04/abalt_fuse6)
+constexpr int kFuseMaskGather = 6;
+
+// flat parameter offsets, NeRF.named_parameters() order (packing.py param_offsets)
+struct POff {
+    int w[12], b[12], fan[12];
+};
+constexpr POff make_poff() {
+    POff p{};
+    const int rows[12] = {256, 256, 256, 256, 256, 256, 256, 256, 256, 128, 1, 3};
+    const int fans[12] = {63, 256, 256, 256, 319, 256, 256, 256, 256, 283, 256, 128};
+    int o = 0;
+    for (int i = 0; i < 12; ++i) {
+        p.w[i] = o;
+        p.fan[i] = fans[i];
+        o += rows[i] * fans[i];
+        p.b[i] = o;
+        o += rows[i];
+    }
+    return p;
+}
+constexpr POff kP = make_poff();
+static_assert(kP.b[11] + 3 == 595844, "parameter count");
+// layer ids: 0..7 = xyz_encoding_1..8, 8 = final, 9 = dir, 10 = sigma, 11 = rgb
+
+__device__ __forceinline__ int pe_feature(int g, int h, int np) {
+    if (g == 0) return h;
+    if (g == 1) return h == 0 ? 2 : -1;
+    if (g < 2 + np) { const int m = g - 2 + np * h; return 3 + 6 * (m / 3) + m % 3; }
+    if (g < 2 + 2 * np) { const int m = g - 2 - np + np * h; return 6 + 6 * (m / 3) + m % 3; }
+    return -1;
+}
+
+struct WgSeg {
+    const float* base;   // segment start (block-native)
+    int kind, width;     // SegKind, columns
+};
+
+struct WgTask {
+    WgSeg a, b;          // a = gradient (M = a.width), b = input (N = b.width)
+    int wm, wn;          // wave grid (wm * wn == 4)
+    int G;               // workgroups
+    int64_t slab;        // slab offset (floats) of workgroup 0
+    int id;              // task id: selects the gradient destination and the kernel shape
+    int stat;            // f16x3: stats slot of the gradient operand (layout.h NR_STATS)
+    int fuse;            // f16x3: index (in WgArgs::task) of the task whose output this task's
+                         // workgroups also compute (same block ranges, its own slab), or -1
+    int pa, pb;          // slab row / column order (wgrad4_kernel): 1 natural; V: each
+                         // 32V-wide chunk holds its V interleaved MFMA tiles one after
+                         // another (w4_unperm)
+};
+
+struct WgArgs {
+    WgTask task[kTasks];
+    int wg_start[kTasks + 1];
+    int nb, n;
+    float* slab;
+    bool x3;             // segments in the bf16x6 pipeline's N16 layout (x3.h)
+    const float* stats;  // f16x3: max |gradient| per segment (mlp_bwd3.hip), else null
+    // optional (active.hip, split arithmetics' wgrad3_body only): the ascending
+    // list of the samples with a nonzero output gradient and its length m on
+    // the device.  The gradient segments (mlp_bwd3.hip *_active) then hold
+    // position q's rows at q; the split-K ranges cover the ceil(m / 32) blocks
+    // of positions, and the input operands are gathered from sample slist[q]
+    const int32_t* slist; const int32_t* scount;
+};
+
+// samples (positions) a launch works on
+__device__ __forceinline__ int wg_m(const WgArgs& a) {
+    return a.slist ? __builtin_amdgcn_readfirstlane(*a.scount) : a.n;
+}
+// blocks of positions a launch's split-K ranges cover
+__device__ __forceinline__ int wg_nact(const WgArgs& a) {
+    return a.slist ? (wg_m(a) + 31) / 32 : a.nb;
+}
+
+// f16x3: the gradient operand of a task is scaled by 2^(kWT - e(max |dz|)) so
+// its largest element sits in [2^kWT, 2^(kWT+1)) < 65504; the input operand
+// (activations, |x| < 65504) is split unscaled.  The reduction divides the
+// weight part of the slab sums by the same power of two (bias sums come from
+// the unscaled values).
+__device__ __forceinline__ float task_scale(const WgArgs& a, const WgTask& T) {
+#if NR_F16
+    constexpr int kWT = 14;
+    return x3::pow2_norm(a.stats[T.stat], kWT, 126);
+#else
+    (void)a; (void)T;
+    return 1.f;
+#endif
+}
+
+}  // namespace

@@ -3,6 +3,9 @@
 # or on the base objects (bf16x6 + exact fp32 + shared kernels, 4th arg "base"):
 #   bash scripts/build_ab.sh <name> "<object...: mlp_fwd3 mlp_bwd3 wgrad ...>" "<-DFLAGS>" [base]
 # -> ablibs/libnerf_pl_amd_<name>.so (selected at run time with NERF_PL_AMD_LIB)
+# (wgrad.hip has no experiment defines left -- NR_W3_* / NR_W4_* / NR_WGRAD_TARGET_WG*
+# / NR_WGRAD_FUSE_MASK* were last accepted by commit d1ec9da; to A/B its tuned
+# constants, edit wgrad_common.h in a second checkout)
 set -eu
 name=$1; objs_ab=$2; flags=$3; kind=${4:-h3}
 HIPFLAGS="-O3 -std=c++17 -fPIC -ffp-contract=off -fno-slp-vectorize --offload-arch=gfx950 -Wall -Wno-unused-function"
