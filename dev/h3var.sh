@@ -3,6 +3,7 @@
 # builds dev/libh3_<name>.so (fwd3 + bwd3 + wgrad, NR_F16=1) for dev/time_h3var.py
 # (the flags now reach x3.h / mlp_fwd3.hip / mlp_bwd3.hip only: wgrad.hip's own
 # experiment defines, NR_W3_* / NR_W4_*, were removed after commit d1ec9da)
+# (of the fused MLP kernels' defines only NR_BWD_W2 is still accepted; 0be27df last built the rest)
 set -e
 name=$1; shift
 /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC -ffp-contract=off -fno-slp-vectorize --offload-arch=gfx950 \

@@ -120,7 +120,7 @@ struct FwdArgs {
 template <int MODE, bool SIGMA_ONLY, bool LIST = false>
 __global__ void __launch_bounds__(64 * kWaves, 1) mlp_fwd_kernel(FwdArgs a) {
     constexpr bool EMB = MODE == FWD_EMB;
-    constexpr bool ROWS = NR_F32_ROWS && !SIGMA_ONLY;
+    constexpr bool ROWS = !SIGMA_ONLY;
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
     const int h = lane >> 5;

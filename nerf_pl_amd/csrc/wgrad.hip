@@ -369,9 +369,9 @@ int wgrad_launch(bool x3, bool sigma_only, const float* save, const float* grad_
     else if (x3) wgrad3_kernel<false, false><<<a.wg_start[kTasks], kThreads, 0, st>>>(a);
     // the full graph's inputs are sample-major rows (mlp_fwd.hip ROWS), the
     // sigma-only graph's block-native
-    else if (slist && gather && !sigma_only && NR_F32_ROWS) wgrad_kernel<true, true><<<a.wg_start[kTasks], kThreads, 0, st>>>(a);
+    else if (slist && gather && !sigma_only) wgrad_kernel<true, true><<<a.wg_start[kTasks], kThreads, 0, st>>>(a);
     else if (slist && gather) wgrad_kernel<true, false><<<a.wg_start[kTasks], kThreads, 0, st>>>(a);
-    else if (!sigma_only && NR_F32_ROWS) wgrad_kernel<false, true><<<a.wg_start[kTasks], kThreads, 0, st>>>(a);
+    else if (!sigma_only) wgrad_kernel<false, true><<<a.wg_start[kTasks], kThreads, 0, st>>>(a);
     else wgrad_kernel<false, false><<<a.wg_start[kTasks], kThreads, 0, st>>>(a);
 #endif
     NR_LAUNCH_CHECK("nr_wgrad");

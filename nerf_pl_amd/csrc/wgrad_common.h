@@ -3,6 +3,67 @@
 #pragma once
 #include "x3.h"
 
+namespace x3 {
+
+// ---- 32x32x16 helpers of the split-operand kernels ---------------------------
+__device__ __forceinline__ f32x16 mfma32(const p8& a, const p8& b, f32x16 c) {
+#if NR_F16
+    return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
+#else
+    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
+#endif
+}
+
+// acc += A * B, small products first; a = the A pieces (hi[, mid], lo)
+__device__ __forceinline__ f32x16 mfma_xp(const p8 (&a)[kNP], const Pieces& b, f32x16 acc) {
+#if NR_F16
+    acc = mfma32(a[1], b.hi, acc);
+    acc = mfma32(a[0], b.lo, acc);
+    acc = mfma32(a[0], b.hi, acc);
+#elif NR_BF1
+    acc = mfma32(a[0], b.hi, acc);
+#else
+    acc = mfma32(a[2], b.hi, acc);
+    acc = mfma32(a[0], b.lo, acc);
+    acc = mfma32(a[1], b.mid, acc);
+    acc = mfma32(a[1], b.hi, acc);
+    acc = mfma32(a[0], b.mid, acc);
+    acc = mfma32(a[0], b.hi, acc);
+#endif
+    return acc;
+}
+
+// acc[j] += A * B[j] for NJ accumulators sharing the A pieces, product-major
+template <int NJ>
+__device__ __forceinline__ void mfma_xp_multi(const p8 (&a)[kNP], const Pieces (&b)[NJ], f32x16* acc) {
+#if NR_F16
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) acc[j] = mfma32(a[1], b[j].hi, acc[j]);
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) acc[j] = mfma32(a[0], b[j].lo, acc[j]);
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) acc[j] = mfma32(a[0], b[j].hi, acc[j]);
+#elif NR_BF1
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) acc[j] = mfma32(a[0], b[j].hi, acc[j]);
+#else
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) acc[j] = mfma32(a[2], b[j].hi, acc[j]);
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) acc[j] = mfma32(a[0], b[j].lo, acc[j]);
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) acc[j] = mfma32(a[1], b[j].mid, acc[j]);
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) acc[j] = mfma32(a[1], b[j].hi, acc[j]);
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) acc[j] = mfma32(a[0], b[j].mid, acc[j]);
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) acc[j] = mfma32(a[0], b[j].hi, acc[j]);
+#endif
+}
+
+}  // namespace x3
+
 namespace {
 
 constexpr int kTasks = 14;

@@ -18,7 +18,7 @@
 // [lane 64][8] bf16 = 24 KiB; tile t = output rows 16t .. 16t+15 of the half.
 // A weight table TAB gives TAB::off(q), the byte offset of group q.
 //
-// wgrad.hip's weight-gradient GEMMs use the 32x32x16 helpers at the end.
+// wgrad.hip's weight-gradient GEMMs use the 32x32x16 helpers of wgrad_common.h.
 //
 // NR_F16 = 1 builds the same kernels as "f16x3" (the 3xTF32 scheme on CDNA4's
 // fp16 matrix cores): each operand is split into two fp16 pieces x = hi + lo
@@ -36,19 +36,6 @@
 #include <utility>
 #include "layout.h"
 
-// NR_X3_DBG (timing experiments only, never in the shipped build):
-// 1 = no barrier, 2 = no DMA wait and no barrier, 3 = no DMA at all,
-// 4 = no MFMA (fragments still read), 5 = no B split between k-steps,
-// 8 = clock stamps (mlp_fwd3.hip writes s_memtime / s_memrealtime deltas),
-// 9 = no saved-activation / gradient stores (store_n16)
-#ifndef NR_X3_DBG
-#define NR_X3_DBG 0
-#endif
-// NR_X3_SGB: interleave one MFMA with this many VALU instructions inside a
-// tile (sched_group_barrier); 0 leaves the order to the scheduler
-#ifndef NR_X3_SGB
-#define NR_X3_SGB 1
-#endif
 #ifndef NR_F16
 #define NR_F16 0
 #endif
@@ -86,10 +73,7 @@ typedef f16x2 p2;
 typedef _Float16 p1;
 constexpr int kNP = 2;                         // pieces per operand
 constexpr int kNProd = 3;                      // piece products per fp32 product
-#ifndef NR_H3_WSCALE
-#define NR_H3_WSCALE 8
-#endif
-constexpr int kWScale = NR_H3_WSCALE;          // packed weights carry 2^kWScale
+constexpr int kWScale = 8;                     // packed weights carry 2^kWScale
 #elif NR_BF1
 typedef bf16x8 p8;
 typedef bf16x2 p2;
@@ -120,28 +104,19 @@ constexpr int kTiles = 8;                          // output tiles (16 rows) per
 // q is consumed, and the wait for it also waits for every older store (vmcnt
 // retires in issue order), so a deeper ring gives the saved-activation stores
 // more time to be acknowledged.  f16x3 groups are 16 KiB: 6 slots fit.
-#ifndef NR_X3_SLOTS
-#define NR_X3_SLOTS (NR_F16 ? 6 : (NR_BF1 ? 8 : 4))
-#endif
-constexpr int kSlots = NR_X3_SLOTS;
+constexpr int kSlots = NR_F16 ? 6 : (NR_BF1 ? 8 : 4);
 constexpr int kSlotBytes = kNP * kTiles * 1024;    // pieces x 8 tiles x 1 KiB
 constexpr int kDma = kNP * kTiles / kWaves;        // DMA instructions per wave per group
 static_assert(kDma * kWaves == kNP * kTiles, "a group's DMA must split evenly over the waves");
-// Merged ring (NR_X3_MERGE): the groups of one k-step (both output halves of a
-// 256-wide layer) share one ring slot of 2 groups and ONE hand-over (wait +
+// Merged ring (f16x3 and bf16; bf16x6 keeps one ring slot per group): the
+// groups of one k-step (both output halves of a 256-wide layer) share one ring slot of 2 groups and ONE hand-over (wait +
 // barrier) instead of one per group; the packed layout is unchanged (the two
 // halves are adjacent).  TAB::sg(q) maps group q to its k-step ("super-group"),
 // TAB::first(G) / TAB::size(G) give a super-group's first group and group
 // count.  The DMA of super-group G + kSS - 1 is issued during G.  Halves the
 // barriers of the 256-wide layers (dev/mb_w8.hip "32 KiB groups").
-#ifndef NR_X3_MERGE
-#define NR_X3_MERGE (NR_F16 || NR_BF1)
-#endif
-constexpr bool kMerge = NR_X3_MERGE;
-#ifndef NR_X3_SSLOTS
-#define NR_X3_SSLOTS (NR_F16 ? 3 : (NR_BF1 ? 6 : 2))
-#endif
-constexpr int kSS = NR_X3_SSLOTS;                  // super-slots of the merged ring
+constexpr bool kMerge = NR_F16 || NR_BF1;
+constexpr int kSS = NR_F16 ? 3 : (NR_BF1 ? 6 : 2); // super-slots of the merged ring
 // the DMA issued during super-group G must be for G + 2 or later: for G + 1
 // (kSS = 2) the hand-over's vmcnt, which leaves the current half's stores in
 // flight, can leave that DMA's last instructions in flight too (measured: a
@@ -221,7 +196,7 @@ __device__ __forceinline__ Dma make_dma(const char* packed, int64_t bytes, char*
 // DMA instruction k (of kDma) of this wave for group Q: fragment i = wave + 4k
 template <class TAB, int Q, int QEND>
 __device__ __forceinline__ void dma_one(const Dma& d, int k) {
-    if constexpr (Q < QEND && NR_X3_DBG != 3) {
+    if constexpr (Q < QEND) {
         const int i = d.wave + kWaves * k;
         __builtin_amdgcn_raw_ptr_buffer_load_lds(
             d.rsrc, (__attribute__((address_space(3))) void*)(d.ring + slot_off<TAB, Q>() + i * 1024), 16,
@@ -251,9 +226,8 @@ __device__ __forceinline__ void prologue(const Dma& d) {
 // flight too; older stores are waited for (they have had a group to land).
 template <class TAB, int Q, int QEND, int EXTRA = 0>
 __device__ __forceinline__ void ring_enter() {
-    if constexpr (NR_X3_DBG < 2)
-        asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(wait_count<TAB, Q, QEND>() + EXTRA) : "memory");
-    if constexpr (NR_X3_DBG == 0) __builtin_amdgcn_s_barrier();
+    asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(wait_count<TAB, Q, QEND>() + EXTRA) : "memory");
+    __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
 }
 
@@ -277,18 +251,11 @@ __device__ __forceinline__ void split2(float x0, float x1, bf16x2& hi, bf16x2& m
 // fp32.  The residual is one v_fma_mix_f32 per value (-hi as an fp16 operand
 // times 1.0 plus x, a single exact rounding) instead of a conversion and a
 // subtraction: the split is VALU-issue-bound between MFMAs.
-#ifndef NR_H3_MIX
-#define NR_H3_MIX 1
-#endif
 __device__ __forceinline__ void split2h(float x0, float x1, f16x2& hi, f16x2& lo) {
     hi = __builtin_convertvector((f32x2){x0, x1}, f16x2);
-#if NR_H3_MIX
     float r0, r1;
     asm("v_fma_mix_f32 %0, -%1, 1.0, %2 op_sel_hi:[1,0,0]" : "=v"(r0) : "v"(hi), "v"(x0));
     asm("v_fma_mix_f32 %0, -%1, 1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r1) : "v"(hi), "v"(x1));
-#else
-    const float r0 = x0 - (float)hi[0], r1 = x1 - (float)hi[1];
-#endif
     lo = __builtin_convertvector((f32x2){r0, r1}, f16x2);
 }
 
@@ -399,16 +366,12 @@ __device__ __forceinline__ void rd_frag(char* ring, int lane, int t, Frag& f) {
     for (int k = 0; k < kNP; ++k) f.p[k] = *reinterpret_cast<const p8*>(s + k * kTiles * 1024);
 }
 
-// LDS fragment lookahead in tiles: the weight fragments of tile t + kPF are
-// read while tile t multiplies (NR_X3_PF = 2 hands the next group over one
-// tile earlier and keeps a third fragment set, 8 more VGPRs)
-#ifndef NR_X3_PF
-#define NR_X3_PF 1
-#endif
-constexpr int kPF = NR_X3_PF;
-static_assert(kPF >= 1 && kPF <= 2, "fragment lookahead of 1 or 2 tiles");
-// the fragments of the next group's first kPF tiles, carried between groups
-struct Ahead { Frag f[kPF]; };
+// VALU instructions interleaved with each MFMA inside a tile (group_mm's
+// sched_group_barrier)
+constexpr int kSgb = 1;
+// the tile-0 fragments of the next group, carried between groups (group_mm
+// reads the fragments of tile t + 1 while tile t multiplies)
+typedef Frag Ahead;
 
 // hand group Q over (wait + barrier) and read its tile-0 fragments; in the
 // merged ring a group that shares its predecessor's super-group arrived with
@@ -420,11 +383,6 @@ __device__ __forceinline__ void enter(char* ring, int lane, Frag& f0) {
             ring_enter<TAB, Q, QEND, EXTRA>();
         rd_frag<TAB, Q>(ring, lane, 0, f0);
     }
-}
-template <class TAB, int Q, int QEND, int EXTRA = 0>
-__device__ __forceinline__ void enter(char* ring, int lane, Ahead& a) {
-    enter<TAB, Q, QEND, EXTRA>(ring, lane, a.f[0]);
-    if constexpr (Q < QEND && kPF > 1) rd_frag<TAB, Q>(ring, lane, 1, a.f[1]);
 }
 
 __device__ __forceinline__ f32x4 mfma16(const p8& a, const p8& b, f32x4 c) {
@@ -440,11 +398,6 @@ __device__ __forceinline__ f32x4 mfma16(const p8& a, const p8& b, f32x4 c) {
 // terms first, the accumulators alternating
 template <int NS>
 __device__ __forceinline__ void x6_multi(const Frag& w, const Pieces (&b)[NS], f32x4 (&c)[NS]) {
-    if constexpr (NR_X3_DBG == 4) {
-#pragma unroll
-        for (int j = 0; j < NS; ++j) asm volatile("" ::"v"(w.p[0]), "v"(w.p[kNP - 1]), "v"(b[j].hi));
-        return;
-    }
     auto prod = [&](const p8& a, auto piece) {
 #pragma unroll
         for (int j = 0; j < NS; ++j) c[j] = mfma16(a, piece(b[j]), c[j]);
@@ -476,46 +429,33 @@ struct BiasInit {     // bias[16F + 4g .. +3] (LDS), the same for both sample ti
     }
 };
 
-// one k-group: acc[F0 + t][S] (+)= W_q[t] * B[S] for the 8 output tiles; with
-// INIT the k-group starts from cinit(F, S) instead of acc.  On entry a holds
-// tiles 0 .. kPF-1 of group Q; the fragments of tile t+kPF are read while tile
-// t multiplies, and the hand-over of group Q+1 (wait, barrier, its tile-0
-// read) is done before the MFMAs of tile 8 - kPF, so both the barrier and the
-// first LDS latency of the next group hide under MFMAs in flight.  On exit a
-// holds tiles 0 .. kPF-1 of group Q+1.  hook(t) runs inside tile t; its VALU
-// work is interleaved with the tile's 2 kNProd MFMAs.  EXTRA: the stores the
-// hooks issue before the hand-over tile (left in flight by its vmcnt wait).
-// Accumulators of a tile in AGPRs ("a") or VGPRs ("v"); at two waves per SIMD
-// a wave has 256 registers in all, so the split is the compiler's
-#ifndef NR_X3_ACC_AGPR
-#define NR_X3_ACC_AGPR 1
-#endif
+// the accumulators of a tile are pinned in AGPRs ("a"); at two waves per SIMD a
+// wave has 256 registers in all, so the split is the compiler's
 template <int NS>
 __device__ __forceinline__ void pin_acc(f32x4 (&d)[NS]) {
-#if NR_X3_ACC_AGPR
     if constexpr (NS == 2) {     // one statement for the pair (the round-5 register assignment)
         asm volatile("" : "+a"(d[0]), "+a"(d[1]));
         return;
     }
-#endif
 #pragma unroll
-    for (int j = 0; j < NS; ++j) {
-#if NR_X3_ACC_AGPR
-        asm volatile("" : "+a"(d[j]));
-#else
-        asm volatile("" : "+v"(d[j]));
-#endif
-    }
+    for (int j = 0; j < NS; ++j) asm volatile("" : "+a"(d[j]));
 }
 
+// one k-group: acc[F0 + t][S] (+)= W_q[t] * B[S] for the 8 output tiles; with
+// INIT the k-group starts from cinit(F, S) instead of acc.  On entry a holds
+// tile 0 of group Q; the fragments of tile t+1 are read while tile t
+// multiplies, and the hand-over of group Q+1 (wait, barrier, its tile-0
+// read) is done before the MFMAs of tile 7, so both the barrier and the
+// first LDS latency of the next group hide under MFMAs in flight.  On exit a
+// holds tile 0 of group Q+1.  hook(t) runs inside tile t; its VALU
+// work is interleaved with the tile's 2 kNProd MFMAs.  EXTRA: the stores the
+// hooks issue before the hand-over tile (left in flight by its vmcnt wait).
 template <class TAB, int Q, int QEND, int F0, bool INIT, int EXTRA, typename CInit, typename Hook, int NF,
           int NS>
 __device__ __forceinline__ void group_mm(char* ring, int lane, f32x4 (&acc)[NF][NS],
                                          const Pieces (&b)[NS], CInit& cinit, Hook& hook, Ahead& a) {
-    constexpr int NR = kPF + 1;       // fragment sets in registers
-    Frag f[NR];
-#pragma unroll
-    for (int i = 0; i < kPF; ++i) f[i] = a.f[i];
+    Frag f[2];       // the current tile's fragments and the next one's
+    f[0] = a;
     f32x4 ci[2][NS];
     if constexpr (INIT) {
 #pragma unroll
@@ -523,10 +463,8 @@ __device__ __forceinline__ void group_mm(char* ring, int lane, f32x4 (&acc)[NF][
     }
 #pragma unroll
     for (int t = 0; t < kTiles; ++t) {
-        const int tn = t + kPF;
-        if (tn < kTiles) rd_frag<TAB, Q>(ring, lane, tn, f[tn % NR]);
-        else if (tn == kTiles) enter<TAB, Q + 1, QEND, EXTRA>(ring, lane, a.f[0]);
-        else if constexpr (Q + 1 < QEND) rd_frag<TAB, Q + 1>(ring, lane, tn - kTiles, a.f[tn - kTiles]);
+        if (t + 1 < kTiles) rd_frag<TAB, Q>(ring, lane, t + 1, f[(t + 1) & 1]);
+        else enter<TAB, Q + 1, QEND, EXTRA>(ring, lane, a);
         if constexpr (INIT) {
             if (t + 1 < kTiles) {
 #pragma unroll
@@ -539,19 +477,17 @@ __device__ __forceinline__ void group_mm(char* ring, int lane, f32x4 (&acc)[NF][
 #pragma unroll
             for (int j = 0; j < NS; ++j) d[j] = ci[t & 1][j];
         }
-        x6_multi<NS>(f[t % NR], b, d);
+        x6_multi<NS>(f[t & 1], b, d);
         // keep the tile's MFMAs in this tile: MFMA intrinsics have no side
         // effects, so without an ordered use the instruction selector may
         // float them anywhere in the (huge) basic block
         pin_acc<NS>(d);
         hook(t);
-#if NR_X3_SGB
 #pragma unroll
         for (int i = 0; i < NS * kNProd; ++i) {
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);          // MFMA
-            __builtin_amdgcn_sched_group_barrier(0x002, NR_X3_SGB, 0);  // VALU
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);     // MFMA
+            __builtin_amdgcn_sched_group_barrier(0x002, kSgb, 0);  // VALU
         }
-#endif
         __builtin_amdgcn_sched_barrier(0);
     }
 }
@@ -590,7 +526,6 @@ struct NoSide {
 
 template <typename GetU, int s, int NS>
 __device__ __forceinline__ void split_unit(GetU& getu, IC<s>, int u, Pieces (&bn)[NS]) {
-    if constexpr (NR_X3_DBG == 5) return;
     const int sb = u >> 2, p = u & 3;
     float x0, x1;
     getu(IC<s>(), sb, p, x0, x1);
@@ -619,7 +554,7 @@ __host__ __device__ constexpr int unit_at(int t) {
     else return t >= 3 && t < 3 + 2 * NS ? 2 * NS * HF + t - 3 : -1;
 }
 // the tile whose start hands the next group over (x3.h group_mm)
-constexpr int kHandTile = kTiles - kPF;
+constexpr int kHandTile = kTiles - 1;
 // stores a storing getter issues before the hand-over tile of its group: one
 // per odd unit, or (PAIRED: the two halves of a 128-B row line together, x3.h
 // store_row_pair) two per unit p = 3
@@ -701,9 +636,6 @@ __device__ __forceinline__ float acc_b(const f32x4 (&X)[NF][NS], int s, int sb, 
 // are re-read only by a later kernel, and streaming them past L2 keeps the
 // weight ring's L2 lines resident (f16x3 fine pass: fwd+save 2.86 -> 2.63 ms,
 // dgrad 3.07 -> 2.56 ms)
-#ifndef NR_NT_STORE
-#define NR_NT_STORE 1
-#endif
 // NR_BF1 (plain bf16): a saved segment holds the values rounded to bf16 --
 // exactly what the weight gradient's bf16 MFMA operands are, so nothing is
 // lost.  Chunk (F, S) of a block (16 features x 16 samples, 512 B) is stored
@@ -741,22 +673,10 @@ __host__ __device__ __forceinline__ int64_t bf16_slot(int64_t idx) {
 __device__ __forceinline__ void store_slot(const f32x4& v, float* __restrict__ seg, int64_t idx) {
 #if NR_BF1
     u32x2* p = reinterpret_cast<u32x2*>(seg) + bf16_slot(idx);
-#if NR_X3_DBG == 9
-    asm volatile("" ::"v"(v), "v"(p));
-#elif NR_NT_STORE
     __builtin_nontemporal_store(pack_bf16x4(v), p);
 #else
-    *p = pack_bf16x4(v);
-#endif
-#else
     f32x4* p = reinterpret_cast<f32x4*>(seg) + idx;
-#if NR_X3_DBG == 9
-    asm volatile("" ::"v"(v), "v"(p));
-#elif NR_NT_STORE && NR_ROW_NT
     __builtin_nontemporal_store(v, p);
-#else
-    *p = v;
-#endif
 #endif
 }
 __device__ __forceinline__ void store_n16(const f32x4& v, int F, int S, float* __restrict__ blk,
@@ -766,13 +686,7 @@ __device__ __forceinline__ void store_n16(const f32x4& v, int F, int S, float* _
     return;
 #endif
     f32x4* p = reinterpret_cast<f32x4*>(blk + ((F * 2 + S) * 64 + lane) * 4);
-#if NR_X3_DBG == 9
-    asm volatile("" ::"v"(v), "v"(p));     // timing experiment: no stores
-#elif NR_NT_STORE
     __builtin_nontemporal_store(v, p);     // streamed: keep L2 for the weight ring
-#else
-    *p = v;
-#endif
 }
 
 // A forward activation saved for the weight gradient (f16x3 / bf16x6):
@@ -782,9 +696,6 @@ __device__ __forceinline__ void store_n16(const f32x4& v, int F, int S, float* _
 // the weight gradient then reads any sample's row contiguously, so gathering
 // the samples with a nonzero output gradient (active.hip) moves only their
 // bytes.  The bf16 variant keeps its N16 slots (store_slot, read by LDS-DMA).
-#ifndef NR_ROW_NT
-#define NR_ROW_NT 1      // row stores non-temporal like the N16 ones (A/B knob)
-#endif
 template <int W>
 __device__ __forceinline__ void store_row(const f32x4& v, int F, int S, float* __restrict__ blk,
                                           int lane) {
@@ -792,35 +703,24 @@ __device__ __forceinline__ void store_row(const f32x4& v, int F, int S, float* _
     store_n16(v, F, S, blk, lane);
 #else
     f32x4* p = reinterpret_cast<f32x4*>(blk + (16 * S + (lane & 15)) * W + 16 * F + 4 * (lane >> 4));
-#if NR_X3_DBG == 9
-    asm volatile("" ::"v"(v), "v"(p));
-#elif NR_NT_STORE && NR_ROW_NT
     __builtin_nontemporal_store(v, p);
-#else
-    *p = v;
-#endif
 #endif
 }
 
-// NR_ROW_PAIR (the row stores of the full graph's forward): 0 = each 64-B
-// half of a sample's 128-B row line stored as soon as its tile is split (two
-// units apart; round 3); 1 = both halves stored back to back; 2 (shipped) =
-// whole lines: the odd tile's values rotated by 8 lanes within each 16-lane
-// row (DPP row_ror:8 with bank masks), so that one store writes 8 samples x
-// 128 B.  Measured (profiles/r04/ab_rowpair, abalt_pair2): the fine forward's
+// The row stores of the full graph's forward write whole 128-B row lines:
+// the odd tile's values rotated by 8 lanes within each 16-lane row (DPP
+// row_ror:8 with bank masks), so that one store writes 8 samples x 128 B,
+// instead of each 64-B half of a line as soon as its tile is split.
+// Measured (profiles/r04/ab_rowpair, abalt_pair2): the fine forward's
 // WRITE_SIZE 10.63 -> 8.33 GB (1.30x -> 1.02x its 8.18 GB of activations),
 // its time unchanged, the data gradient that follows it 1.54 -> 1.45 ms and
 // the cfg2 step +1.5% (three alternating rounds on one box)
-#ifndef NR_ROW_PAIR
-#define NR_ROW_PAIR 2
-#endif
-constexpr bool kRowPair = NR_ROW_PAIR != 0 && !NR_BF1;
+constexpr bool kRowPair = !NR_BF1;
 
 // tiles F0 (even) and F0 + 1 of sample tile S: the 128-B row line [16 F0, 16 F0 + 32)
 template <int W>
 __device__ __forceinline__ void store_row_pair(const f32x4& t0, const f32x4& t1, int F0, int S,
                                                float* __restrict__ blk, int lane) {
-#if NR_ROW_PAIR == 2
     // lane (g, j): A = samples 16S + (j & 7), B = samples 16S + 8 + (j & 7);
     // in A lanes j < 8 write their own tile F0, lanes j >= 8 tile F0 + 1 of
     // lane j - 8; in B the other way round
@@ -835,19 +735,8 @@ __device__ __forceinline__ void store_row_pair(const f32x4& t0, const f32x4& t1,
     const int hi = j >> 3;
     f32x4* pa = reinterpret_cast<f32x4*>(blk + (16 * S + (j & 7)) * W + 16 * F0 + 16 * hi + 4 * g);
     f32x4* pb = reinterpret_cast<f32x4*>(blk + (16 * S + 8 + (j & 7)) * W + 16 * F0 + 16 * (1 - hi) + 4 * g);
-#if NR_X3_DBG == 9
-    asm volatile("" ::"v"(a), "v"(b), "v"(pa), "v"(pb));
-#elif NR_NT_STORE && NR_ROW_NT
     __builtin_nontemporal_store(a, pa);
     __builtin_nontemporal_store(b, pb);
-#else
-    *pa = a;
-    *pb = b;
-#endif
-#else
-    store_row<W>(t0, F0, S, blk, lane);
-    store_row<W>(t1, F0 + 1, S, blk, lane);
-#endif
 }
 
 // ReLU mask bits of a post-ReLU activation: word F >> 2 of the lane, bit
@@ -859,63 +748,6 @@ __device__ __forceinline__ void mask_bits(const f32x4& v, int F, int S, uint32_t
 }
 __device__ __forceinline__ float mask_keep(float x, const uint32_t (&w)[4], int F, int S, int r) {
     return nr_mask_bit(x, w[F >> 2], 8 * (F & 3) + 4 * S + r);
-}
-
-// ---- 32x32x16 helpers (wgrad.hip) ------------------------------------------
-__device__ __forceinline__ f32x16 mfma32(const p8& a, const p8& b, f32x16 c) {
-#if NR_F16
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-#else
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-#endif
-}
-
-// acc += A * B, small products first; a = the A pieces (hi[, mid], lo)
-__device__ __forceinline__ f32x16 mfma_xp(const p8 (&a)[kNP], const Pieces& b, f32x16 acc) {
-#if NR_F16
-    acc = mfma32(a[1], b.hi, acc);
-    acc = mfma32(a[0], b.lo, acc);
-    acc = mfma32(a[0], b.hi, acc);
-#elif NR_BF1
-    acc = mfma32(a[0], b.hi, acc);
-#else
-    acc = mfma32(a[2], b.hi, acc);
-    acc = mfma32(a[0], b.lo, acc);
-    acc = mfma32(a[1], b.mid, acc);
-    acc = mfma32(a[1], b.hi, acc);
-    acc = mfma32(a[0], b.mid, acc);
-    acc = mfma32(a[0], b.hi, acc);
-#endif
-    return acc;
-}
-
-// acc[j] += A * B[j] for NJ accumulators sharing the A pieces, product-major
-template <int NJ>
-__device__ __forceinline__ void mfma_xp_multi(const p8 (&a)[kNP], const Pieces (&b)[NJ], f32x16* acc) {
-#if NR_F16
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) acc[j] = mfma32(a[1], b[j].hi, acc[j]);
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) acc[j] = mfma32(a[0], b[j].lo, acc[j]);
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) acc[j] = mfma32(a[0], b[j].hi, acc[j]);
-#elif NR_BF1
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) acc[j] = mfma32(a[0], b[j].hi, acc[j]);
-#else
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) acc[j] = mfma32(a[2], b[j].hi, acc[j]);
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) acc[j] = mfma32(a[0], b[j].lo, acc[j]);
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) acc[j] = mfma32(a[1], b[j].mid, acc[j]);
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) acc[j] = mfma32(a[1], b[j].hi, acc[j]);
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) acc[j] = mfma32(a[0], b[j].mid, acc[j]);
-#pragma unroll
-    for (int j = 0; j < NJ; ++j) acc[j] = mfma32(a[0], b[j].hi, acc[j]);
-#endif
 }
 
 // power of two 2^(target - e), e = the binary exponent of m (m in [2^e, 2^(e+1))),
