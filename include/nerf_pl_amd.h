@@ -479,6 +479,20 @@ int nr_sm_backward(const float* g_out, void* workspace, int method, float delta,
 /* Test hook: one v_mfma_f32_32x32x2_f32 on A (32x2), B (2x32) -> D (32x32). */
 int nr_probe_mfma32(const float* a, const float* b, float* d, void* stream);
 
+/* Test hook: the draws the kernels make in-register when their replay
+ * pointers are NULL (nr_coarse_z u, nr_composite_* noise, nr_sample_pdf u /
+ * jitter).  Philox4x32-10 with counter (idx low word, idx high word,
+ * rng_stream, 0 for a uniform | 1 for a normal) and key (seed low word, seed
+ * high word); x, y the first two output words:
+ *   uniform = (x >> 8) * 2^-24                                  in [0, 1)
+ *   normal  = sqrt(-2 ln(((x >> 8) + 1) * 2^-24)) * cos(2 pi (y >> 8) * 2^-24)
+ * rng_stream: 0 perturb, 1 coarse noise, 2 u, 3 jitter, 4 fine noise, each
+ * indexed by the element's row-major position in its (n_rays, samples) draw.
+ * uniform_out[i] / normal_out[i] (n floats each, either may be NULL) are the
+ * draws at idx0 + i. */
+int nr_probe_rand(uint64_t seed, int rng_stream, uint64_t idx0, int64_t n, float* uniform_out,
+                  float* normal_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -116,6 +116,7 @@ SIGNATURES = {
     "nr_embed": [_p, _i64, _i, _p, _p],
     "nr_pack": [_p, _p, _i64, _p, _p],
     "nr_probe_mfma32": [_p, _p, _p, _p],
+    "nr_probe_rand": [_u64, _i, _u64, _i64, _p, _p, _p],
     "nr_layout_query": [_i],
     "nr_last_error": [],
 }

@@ -1,5 +1,6 @@
 // Self-checks exported through the C ABI: layout constants (callable without a
-// GPU) and an MFMA lane-map probe (tests/test_gpu_kernels.py).
+// GPU), an MFMA lane-map probe (tests/test_gpu_kernels.py) and a probe of the
+// in-kernel Philox draws (tests/test_gpu_philox.py).
 #include "layout.h"
 
 NR_API int64_t nr_layout_query(int what) {
@@ -32,7 +33,29 @@ __global__ void probe_mfma_kernel(const float* a_in, const float* b_in, float* d
     c = nr_mfma32(a, b, c);
     for (int r = 0; r < 16; ++r) d_out[nr_acc_row(r, l >> 5) * 32 + (l & 31)] = c[r];
 }
+
+// The in-kernel draws themselves (common.h), element i at counter idx0 + i:
+// what coarse_z / composite / sample_pdf draw when their replay pointers are
+// null (tests/test_gpu_philox.py)
+__global__ void probe_rand_kernel(uint64_t seed, uint32_t stream, uint64_t idx0, int64_t n,
+                                  float* __restrict__ uniform_out,
+                                  float* __restrict__ normal_out) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    if (uniform_out) uniform_out[i] = nr_rand_uniform(seed, stream, idx0 + (uint64_t)i);
+    if (normal_out) normal_out[i] = nr_rand_normal(seed, stream, idx0 + (uint64_t)i);
+}
 }  // namespace
+
+NR_API int nr_probe_rand(uint64_t seed, int stream, uint64_t idx0, int64_t n, float* uniform_out,
+                         float* normal_out, void* stream_) {
+    NR_REQUIRE(n >= 0 && n <= ((int64_t)1 << 31), "nr_probe_rand: bad size");
+    if (n == 0 || (!uniform_out && !normal_out)) return 0;
+    probe_rand_kernel<<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream_>>>(
+        seed, (uint32_t)stream, idx0, n, uniform_out, normal_out);
+    NR_LAUNCH_CHECK("nr_probe_rand");
+    return 0;
+}
 
 NR_API int nr_probe_mfma32(const float* a, const float* b, float* d, void* stream) {
     probe_mfma_kernel<<<1, 64, 0, (hipStream_t)stream>>>(a, b, d);

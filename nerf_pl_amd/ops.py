@@ -348,6 +348,17 @@ def probe_mfma32(a, b):
     return d.view(32, 32)
 
 
+def probe_rand(seed, stream, n, idx0=0, device=None):
+    """(uniform (n,), normal (n,)): the kernels' in-register Philox draws of
+    ``stream`` (rng.STREAM_*) at counters idx0 .. idx0 + n - 1 (csrc/common.h
+    nr_rand_uniform / nr_rand_normal)."""
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else device
+    u = torch.empty(n, device=dev)
+    nrm = torch.empty(n, device=dev)
+    call("nr_probe_rand", seed, int(stream), idx0, n, ptr(u), ptr(nrm), stream_of(dev))
+    return u, nrm
+
+
 def layout_query(what: int) -> int:
     return int(lib().nr_layout_query(what))
 

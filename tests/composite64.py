@@ -61,7 +61,8 @@ class Composite64:
             # fp32 product, then fp32 sum (render.hip sample_noise, alpha_of)
             s32 = sig + _f32(noise).reshape(n, S) * np.float32(noise_std)
         else:
-            assert noise_std == 0, "the in-kernel Philox draw has no reference here"
+            assert noise_std == 0, ("the in-kernel Philox draw has no reference here: "
+                                    "tests/test_gpu_philox.py proves it equal to replayed noise")
             s32 = sig.copy()
         assert s32.dtype == np.float32
         self.n, self.S, self.s32 = n, S, s32

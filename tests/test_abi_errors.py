@@ -114,6 +114,11 @@ def _cases():
         ("nr_sm_backward", [P, P + 4, 2, 1e-3, 1e-3, 0, 4, 16, P, P, N], NR_EINVAL),
         # a workspace nr_sm_forward never laid out (its n_light would be unchecked)
         ("nr_sm_backward", [P, P + 0x1000, 2, 1e-3, 1e-3, 0, 4, 16, P, P, N], NR_EINVAL),
+        # appended, so that the ids of the cases above (which carry their position) stay
+        ("nr_probe_rand", [7, 1, 0, -1, N, N, N], NR_EINVAL),
+        ("nr_probe_rand", [7, 1, 0, 2 ** 31 + 1, P, P, N], NR_EINVAL),
+        ("nr_probe_rand", [7, 1, 0, 0, N, N, N], 0),
+        ("nr_probe_rand", [2 ** 64 - 1, 4, 2 ** 64 - 1, 5, N, N, N], 0),      # nothing asked for
     ]
     return c
 

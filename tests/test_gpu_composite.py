@@ -239,8 +239,10 @@ def test_forward_matches_oracle(regime, white_back):
 
 def test_in_kernel_noise_is_deterministic():
     """noise=None with noise_std > 0 draws Philox normals in the kernel: the
-    same (seed, stream) gives the same bits in two calls, forward and backward
-    (the backward re-draws what the forward drew), and another seed differs"""
+    same (seed, stream) gives the same bits in two calls, forward and backward,
+    and another seed differs.  That the backward re-draws what the forward
+    drew, and what those draws are, is tests/test_gpu_philox.py's: there the
+    in-kernel draw has a reference (both kernels against replay of the draws)"""
     from nerf_pl_amd import ops
     for S, n in ((65, 37), (193, 5)):
         k = case("typical", S, n)
