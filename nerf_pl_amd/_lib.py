@@ -20,73 +20,52 @@ _i64 = ctypes.c_int64
 _u64 = ctypes.c_uint64
 _f = ctypes.c_float
 
+# The fused-MLP entry points come once per arithmetic: "" exact fp32, then the
+# split-operand objects (ops._SUFFIX).  The bf16 object has no sample lists.
+_ARITHS = ("", "_x3", "_h3", "_b1")
+_LISTING = ("", "_x3", "_h3")
+_FWD = [_p, _p, _p, _i64, _i, _p, _i, _i, _p, _p, _p]
+_FWD_LISTED = [_p, _p, _p, _i64, _i, _i, _p, _p, _p, _p]
+_BWD = [_p, _p, _p, _p, _p, _i64, _p, _p]
+_WGRAD = [_p, _p, _i64, _p, _p, _p]
+
+
+def _listed(args):
+    """``args`` with (samples, count) in front of the stream"""
+    return args[:-1] + [_p, _p] + args[-1:]
+
+
+def _families():
+    rows = {}
+    for s in _ARITHS:
+        rows["nr_mlp_fwd" + s] = _FWD
+        rows["nr_mlp_sigma_points" + s] = [_p, _p, _i64, _p, _p]
+    for s in _ARITHS[1:]:
+        rows["nr_pack" + s] = [_p, _p, _i64, _p, _p, _p]
+        rows["nr_pack_bwd" + s] = [_p, _p, _i64, _p, _p]
+    for s in _LISTING:
+        rows["nr_mlp_fwd_listed" + s] = _FWD_LISTED
+    for base, args in (("nr_mlp_bwd", _BWD), ("nr_wgrad", _WGRAD)):
+        for graph in ("", "_sigma"):
+            for s in _ARITHS:
+                rows[base + graph + s] = args
+            for mode in ("_active", "_listed"):
+                for s in _LISTING:
+                    rows[base + graph + mode + s] = _listed(args)
+    return rows
+
+
 # name -> argtypes; every entry returns int (0 = ok) unless listed in _RESTYPES
 SIGNATURES = {
-    "nr_mlp_fwd": [_p, _p, _p, _i64, _i, _p, _i, _i, _p, _p, _p],
-    "nr_mlp_sigma_points": [_p, _p, _i64, _p, _p],
+    **_families(),
     "nr_fwd3_packed_bytes": [],
-    "nr_pack_x3": [_p, _p, _i64, _p, _p, _p],
-    "nr_mlp_fwd_x3": [_p, _p, _p, _i64, _i, _p, _i, _i, _p, _p, _p],
-    "nr_mlp_sigma_points_x3": [_p, _p, _i64, _p, _p],
-    "nr_pack_bwd_x3": [_p, _p, _i64, _p, _p],
-    "nr_mlp_bwd_x3": [_p, _p, _p, _p, _p, _i64, _p, _p],
-    "nr_mlp_bwd_sigma_x3": [_p, _p, _p, _p, _p, _i64, _p, _p],
-    "nr_wgrad_x3": [_p, _p, _i64, _p, _p, _p],
-    "nr_wgrad_sigma_x3": [_p, _p, _i64, _p, _p, _p],
     "nr_fwd3_packed_bytes_h3": [],
-    "nr_pack_h3": [_p, _p, _i64, _p, _p, _p],
-    "nr_mlp_fwd_h3": [_p, _p, _p, _i64, _i, _p, _i, _i, _p, _p, _p],
-    "nr_mlp_sigma_points_h3": [_p, _p, _i64, _p, _p],
-    "nr_pack_bwd_h3": [_p, _p, _i64, _p, _p],
-    "nr_mlp_bwd_h3": [_p, _p, _p, _p, _p, _i64, _p, _p],
-    "nr_mlp_bwd_sigma_h3": [_p, _p, _p, _p, _p, _i64, _p, _p],
-    "nr_wgrad_h3": [_p, _p, _i64, _p, _p, _p],
-    "nr_wgrad_sigma_h3": [_p, _p, _i64, _p, _p, _p],
     "nr_fwd3_packed_bytes_b1": [],
-    "nr_pack_b1": [_p, _p, _i64, _p, _p, _p],
-    "nr_mlp_fwd_b1": [_p, _p, _p, _i64, _i, _p, _i, _i, _p, _p, _p],
-    "nr_mlp_sigma_points_b1": [_p, _p, _i64, _p, _p],
-    "nr_pack_bwd_b1": [_p, _p, _i64, _p, _p],
-    "nr_mlp_bwd_b1": [_p, _p, _p, _p, _p, _i64, _p, _p],
-    "nr_mlp_bwd_sigma_b1": [_p, _p, _p, _p, _p, _i64, _p, _p],
-    "nr_wgrad_b1": [_p, _p, _i64, _p, _p, _p],
-    "nr_wgrad_sigma_b1": [_p, _p, _i64, _p, _p, _p],
     "nr_active_samples": [_p, _i64, _p, _p, _p, _p],
     "nr_active_scratch_ints": [_i64],
-    "nr_mlp_bwd_active_x3": [_p, _p, _p, _p, _p, _i64, _p, _p, _p, _p],
-    "nr_mlp_bwd_active_h3": [_p, _p, _p, _p, _p, _i64, _p, _p, _p, _p],
-    "nr_mlp_bwd_sigma_active_x3": [_p, _p, _p, _p, _p, _i64, _p, _p, _p, _p],
-    "nr_mlp_bwd_sigma_active_h3": [_p, _p, _p, _p, _p, _i64, _p, _p, _p, _p],
-    "nr_wgrad_active_x3": [_p, _p, _i64, _p, _p, _p, _p, _p],
-    "nr_wgrad_active_h3": [_p, _p, _i64, _p, _p, _p, _p, _p],
-    "nr_wgrad_sigma_active_x3": [_p, _p, _i64, _p, _p, _p, _p, _p],
-    "nr_wgrad_sigma_active_h3": [_p, _p, _i64, _p, _p, _p, _p, _p],
-    "nr_mlp_bwd": [_p, _p, _p, _p, _p, _i64, _p, _p],
-    "nr_mlp_bwd_sigma": [_p, _p, _p, _p, _p, _i64, _p, _p],
-    "nr_mlp_bwd_active": [_p, _p, _p, _p, _p, _i64, _p, _p, _p, _p],
-    "nr_mlp_bwd_sigma_active": [_p, _p, _p, _p, _p, _i64, _p, _p, _p, _p],
-    "nr_wgrad_sigma": [_p, _p, _i64, _p, _p, _p],
-    "nr_wgrad_active": [_p, _p, _i64, _p, _p, _p, _p, _p],
-    "nr_wgrad_sigma_active": [_p, _p, _i64, _p, _p, _p, _p, _p],
-    "nr_mlp_fwd_listed": [_p, _p, _p, _i64, _i, _i, _p, _p, _p, _p],
-    "nr_mlp_bwd_listed": [_p, _p, _p, _p, _p, _i64, _p, _p, _p, _p],
-    "nr_mlp_bwd_sigma_listed": [_p, _p, _p, _p, _p, _i64, _p, _p, _p, _p],
-    "nr_wgrad_listed": [_p, _p, _i64, _p, _p, _p, _p, _p],
-    "nr_wgrad_sigma_listed": [_p, _p, _i64, _p, _p, _p, _p, _p],
-    "nr_mlp_fwd_listed_x3": [_p, _p, _p, _i64, _i, _i, _p, _p, _p, _p],
-    "nr_mlp_bwd_listed_x3": [_p, _p, _p, _p, _p, _i64, _p, _p, _p, _p],
-    "nr_mlp_bwd_sigma_listed_x3": [_p, _p, _p, _p, _p, _i64, _p, _p, _p, _p],
-    "nr_wgrad_listed_x3": [_p, _p, _i64, _p, _p, _p, _p, _p],
-    "nr_wgrad_sigma_listed_x3": [_p, _p, _i64, _p, _p, _p, _p, _p],
-    "nr_mlp_fwd_listed_h3": [_p, _p, _p, _i64, _i, _i, _p, _p, _p, _p],
-    "nr_mlp_bwd_listed_h3": [_p, _p, _p, _p, _p, _i64, _p, _p, _p, _p],
-    "nr_mlp_bwd_sigma_listed_h3": [_p, _p, _p, _p, _p, _i64, _p, _p, _p, _p],
-    "nr_wgrad_listed_h3": [_p, _p, _i64, _p, _p, _p, _p, _p],
-    "nr_wgrad_sigma_listed_h3": [_p, _p, _i64, _p, _p, _p, _p, _p],
     "nr_wgrad_workspace_bytes": [_i64],
     "nr_wgrad_dir_feat": [_p, _p, _p],
     "nr_sm_workspace_bytes": [_i64, _i64],
-    "nr_wgrad": [_p, _p, _i64, _p, _p, _p],
     "nr_coarse_z": [_p, _p, _i64, _i, _i, _f, _p, _u64, _p, _p],
     "nr_composite_fwd": [_p, _i, _i, _p, _p, _p, _f, _u64, _i, _i64, _i, _i, _i, _p, _p, _p,
                          _p, _p],

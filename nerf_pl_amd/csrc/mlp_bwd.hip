@@ -192,10 +192,10 @@ __global__ void __launch_bounds__(64 * kWaves, 1) mlp_bwd_kernel(BwdArgs a) {
 }  // namespace
 
 namespace {
-int bwd_launch(const char* name, bool so, const float* packed_bwd, const float* head,
-               const float* out, const float* g_out, const float* save, int64_t n,
-               float* grad_ws, const int32_t* slist, const int32_t* scount, void* stream,
-               bool listed_save = false) {
+template <bool SO, int GM>
+int bwd_launch(const char* name, const float* packed_bwd, const float* head, const float* out,
+               const float* g_out, const float* save, int64_t n, float* grad_ws,
+               const int32_t* slist, const int32_t* scount, void* stream) {
     NR_REQUIRE(n >= 0 && n < (int64_t)1 << 31, "%s: n out of range", name);
     if (n == 0) return 0;
     NR_REQUIRE(packed_bwd && head && out && g_out && save && grad_ws, "%s: null pointer", name);
@@ -204,67 +204,44 @@ int bwd_launch(const char* name, bool so, const float* packed_bwd, const float* 
                "%s: pointers must be 16-byte aligned", name);
     BwdArgs a{packed_bwd, head, out, g_out, save, (int)n, grad_ws, slist, scount};
     const int blocks = (int)((n + 32 * kWaves - 1) / (32 * kWaves));
-    hipStream_t st = (hipStream_t)stream;
-    if (so && slist && listed_save) mlp_bwd_kernel<true, 2><<<blocks, 64 * kWaves, 0, st>>>(a);
-    else if (slist && listed_save) mlp_bwd_kernel<false, 2><<<blocks, 64 * kWaves, 0, st>>>(a);
-    else if (so && slist) mlp_bwd_kernel<true, 1><<<blocks, 64 * kWaves, 0, st>>>(a);
-    else if (so) mlp_bwd_kernel<true, 0><<<blocks, 64 * kWaves, 0, st>>>(a);
-    else if (slist) mlp_bwd_kernel<false, 1><<<blocks, 64 * kWaves, 0, st>>>(a);
-    else mlp_bwd_kernel<false, 0><<<blocks, 64 * kWaves, 0, st>>>(a);
+    mlp_bwd_kernel<SO, GM><<<blocks, 64 * kWaves, 0, (hipStream_t)stream>>>(a);
     NR_LAUNCH_CHECK(name);
     return 0;
 }
 }  // namespace
 
-NR_API int nr_mlp_bwd(const float* packed_bwd, const float* head, const float* out,
-                      const float* g_out, const float* save, int64_t n, float* grad_ws,
-                      void* stream) {
-    return bwd_launch("nr_mlp_bwd", false, packed_bwd, head, out, g_out, save, n, grad_ws,
-                      nullptr, nullptr, stream);
-}
+// The entry points (SIGMA: the sigma-only graph, GM: mlp_bwd_kernel's list mode):
+//   nr_mlp_bwd        every sample of the full graph
+//   nr_mlp_bwd_sigma  the sigma-only graph (g_out column 3 = d sigma, the rgb
+//                     columns ignored): writes dz1..dz8 and the head gradient
+//                     [0, 0, 0, dsigma] for nr_wgrad_sigma
+//   *_active          over the samples nr_active_samples listed: position q of
+//                     every gradient segment holds sample samples[q]'s rows;
+//                     positions past *count are not read
+//   *_listed          the deferred save (nr_mlp_fwd_listed): the listed samples'
+//                     activations saved by position
+// A null list passes when n == 0 here; the split-arithmetic objects
+// (mlp_bwd3.hip) refuse it whatever n.
+#define NR_BWD_ENTRY(NAME, SIGMA)                                                              \
+    NR_API int NAME(const float* packed_bwd, const float* head, const float* out,              \
+                    const float* g_out, const float* save, int64_t n, float* grad_ws,          \
+                    void* stream) {                                                            \
+        return bwd_launch<SIGMA, 0>(#NAME, packed_bwd, head, out, g_out, save, n, grad_ws,     \
+                                    nullptr, nullptr, stream);                                 \
+    }
+#define NR_BWD_LIST_ENTRY(NAME, SIGMA, GM)                                                     \
+    NR_API int NAME(const float* packed_bwd, const float* head, const float* out,              \
+                    const float* g_out, const float* save, int64_t n, float* grad_ws,          \
+                    const int32_t* samples, const int32_t* count, void* stream) {              \
+        NR_REQUIRE(n == 0 || (samples && count), #NAME ": null sample list");                  \
+        return bwd_launch<SIGMA, GM>(#NAME, packed_bwd, head, out, g_out, save, n, grad_ws,    \
+                                     samples, count, stream);                                  \
+    }
 
-// the sigma-only graph (g_out column 3 = d sigma, the rgb columns ignored):
-// writes dz1..dz8 and the head gradient [0, 0, 0, dsigma] for nr_wgrad_sigma
-NR_API int nr_mlp_bwd_sigma(const float* packed_bwd, const float* head, const float* out,
-                            const float* g_out, const float* save, int64_t n, float* grad_ws,
-                            void* stream) {
-    return bwd_launch("nr_mlp_bwd_sigma", true, packed_bwd, head, out, g_out, save, n, grad_ws,
-                      nullptr, nullptr, stream);
-}
-
-// over the samples nr_active_samples listed: position q of every gradient
-// segment holds sample samples[q]'s rows; positions past *count are not read
-NR_API int nr_mlp_bwd_active(const float* packed_bwd, const float* head, const float* out,
-                             const float* g_out, const float* save, int64_t n, float* grad_ws,
-                             const int32_t* samples, const int32_t* count, void* stream) {
-    NR_REQUIRE(n == 0 || (samples && count), "nr_mlp_bwd_active: null sample list");
-    return bwd_launch("nr_mlp_bwd_active", false, packed_bwd, head, out, g_out, save, n, grad_ws,
-                      samples, count, stream);
-}
-
-NR_API int nr_mlp_bwd_sigma_active(const float* packed_bwd, const float* head, const float* out,
-                                   const float* g_out, const float* save, int64_t n,
-                                   float* grad_ws, const int32_t* samples, const int32_t* count,
-                                   void* stream) {
-    NR_REQUIRE(n == 0 || (samples && count), "nr_mlp_bwd_sigma_active: null sample list");
-    return bwd_launch("nr_mlp_bwd_sigma_active", true, packed_bwd, head, out, g_out, save, n,
-                      grad_ws, samples, count, stream);
-}
-
-// the deferred save (nr_mlp_fwd_listed): the listed samples' activations saved by position
-NR_API int nr_mlp_bwd_listed(const float* packed_bwd, const float* head, const float* out,
-                             const float* g_out, const float* save, int64_t n, float* grad_ws,
-                             const int32_t* samples, const int32_t* count, void* stream) {
-    NR_REQUIRE(n == 0 || (samples && count), "nr_mlp_bwd_listed: null sample list");
-    return bwd_launch("nr_mlp_bwd_listed", false, packed_bwd, head, out, g_out, save, n, grad_ws,
-                      samples, count, stream, true);
-}
-
-NR_API int nr_mlp_bwd_sigma_listed(const float* packed_bwd, const float* head, const float* out,
-                                   const float* g_out, const float* save, int64_t n,
-                                   float* grad_ws, const int32_t* samples, const int32_t* count,
-                                   void* stream) {
-    NR_REQUIRE(n == 0 || (samples && count), "nr_mlp_bwd_sigma_listed: null sample list");
-    return bwd_launch("nr_mlp_bwd_sigma_listed", true, packed_bwd, head, out, g_out, save, n,
-                      grad_ws, samples, count, stream, true);
-}
+// (listed in the order that keeps the kernels' places in the code object)
+NR_BWD_LIST_ENTRY(nr_mlp_bwd_sigma_listed, true, 2)
+NR_BWD_LIST_ENTRY(nr_mlp_bwd_listed, false, 2)
+NR_BWD_LIST_ENTRY(nr_mlp_bwd_sigma_active, true, 1)
+NR_BWD_ENTRY(nr_mlp_bwd_sigma, true)
+NR_BWD_LIST_ENTRY(nr_mlp_bwd_active, false, 1)
+NR_BWD_ENTRY(nr_mlp_bwd, false)

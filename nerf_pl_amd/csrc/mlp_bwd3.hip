@@ -581,10 +581,10 @@ NR_API int NR_X3_NAME(nr_pack_bwd)(const float* flat, const int32_t* map, int64_
 }
 
 namespace {
-int bwd3_launch(const char* name, bool sigma_only, const void* packed_bwd, const float* head,
-                const float* out, const float* g_out, const float* save, int64_t n,
-                float* grad_ws, void* stream, const int32_t* slist = nullptr,
-                const int32_t* scount = nullptr, bool listed_save = false) {
+template <bool SO, int GM>
+int bwd3_launch(const char* name, const void* packed_bwd, const float* head, const float* out,
+                const float* g_out, const float* save, int64_t n, float* grad_ws, void* stream,
+                const int32_t* slist = nullptr, const int32_t* scount = nullptr) {
     NR_REQUIRE(n >= 0 && n < (int64_t)1 << 31, "%s: n out of range", name);
     if (n == 0) return 0;
     NR_REQUIRE(packed_bwd && head && out && g_out && save && grad_ws, "%s: null pointer", name);
@@ -595,81 +595,51 @@ int bwd3_launch(const char* name, bool sigma_only, const void* packed_bwd, const
     Bwd3Args a{reinterpret_cast<const char*>(packed_bwd), head, out, g_out, save, (int)n, grad_ws,
                stats, slist, scount};
     const int blocks = (int)((n + 32 * kBlocks - 1) / (32 * kBlocks));
-    hipStream_t st = (hipStream_t)stream;
-#if NR_BF1     // no sample lists for the bf16 variant
-    if (sigma_only) mlp_bwd3_kernel<true, 0><<<blocks, 64 * kWaves, 0, st>>>(a);
-    else mlp_bwd3_kernel<false, 0><<<blocks, 64 * kWaves, 0, st>>>(a);
-#else
-    if (slist && listed_save) {
-        if (sigma_only) mlp_bwd3_kernel<true, 2><<<blocks, 64 * kWaves, 0, st>>>(a);
-        else mlp_bwd3_kernel<false, 2><<<blocks, 64 * kWaves, 0, st>>>(a);
-    } else if (slist) {
-        if (sigma_only) mlp_bwd3_kernel<true, 1><<<blocks, 64 * kWaves, 0, st>>>(a);
-        else mlp_bwd3_kernel<false, 1><<<blocks, 64 * kWaves, 0, st>>>(a);
-    } else {
-        if (sigma_only) mlp_bwd3_kernel<true, 0><<<blocks, 64 * kWaves, 0, st>>>(a);
-        else mlp_bwd3_kernel<false, 0><<<blocks, 64 * kWaves, 0, st>>>(a);
-    }
-#endif
+    mlp_bwd3_kernel<SO, GM><<<blocks, 64 * kWaves, 0, (hipStream_t)stream>>>(a);
     NR_LAUNCH_CHECK(name);
     return 0;
 }
 }  // namespace
 
-NR_API int NR_X3_NAME(nr_mlp_bwd)(const void* packed_bwd, const float* head, const float* out,
-                         const float* g_out, const float* save, int64_t n, float* grad_ws,
-                         void* stream) {
-    return bwd3_launch("nr_mlp_bwd_x3", false, packed_bwd, head, out, g_out, save, n, grad_ws,
-                       stream);
-}
+// The entry points: NR_X3_NAME(BASE) is the exported symbol (SIGMA: the
+// sigma-only graph, GM: mlp_bwd3_kernel's list mode).  Every flavour's messages
+// say BASE "_x3" for the whole-batch calls and BASE alone for the list calls.
+//   nr_mlp_bwd        every sample of the full graph
+//   nr_mlp_bwd_sigma  the sigma-only graph's data gradient (g_out column 3 =
+//                     d sigma; the rgb columns are ignored): save from the
+//                     sigma-only training forward
+//   *_active          the same over the samples nr_active_samples listed
+//                     (samples / count on the device), packed: grad_ws holds
+//                     position q's rows at q -- only the matching
+//                     nr_wgrad*_active entry point (same list) may consume it
+//   *_listed          the deferred save: the same list over a save buffer
+//                     nr_mlp_fwd_listed* wrote by position (masks read by
+//                     position, g_out / out gathered by the list)
+// A null list is refused whatever n; the exact-fp32 object (mlp_bwd.hip) lets
+// it pass when n == 0.
+#define NR_BWD3_ENTRY(BASE, SIGMA)                                                             \
+    NR_API int NR_X3_NAME(BASE)(const void* packed_bwd, const float* head, const float* out,   \
+                                const float* g_out, const float* save, int64_t n,              \
+                                float* grad_ws, void* stream) {                                \
+        return bwd3_launch<SIGMA, 0>(#BASE "_x3", packed_bwd, head, out, g_out, save, n,       \
+                                     grad_ws, stream);                                         \
+    }
+#define NR_BWD3_LIST_ENTRY(BASE, SIGMA, GM)                                                    \
+    NR_API int NR_X3_NAME(BASE)(const void* packed_bwd, const float* head, const float* out,   \
+                                const float* g_out, const float* save, int64_t n,              \
+                                float* grad_ws, const int32_t* samples, const int32_t* count,  \
+                                void* stream) {                                                \
+        NR_REQUIRE(samples && count, #BASE ": null sample list");                              \
+        return bwd3_launch<SIGMA, GM>(#BASE, packed_bwd, head, out, g_out, save, n, grad_ws,   \
+                                      stream, samples, count);                                 \
+    }
 
-// the sigma-only graph's data gradient (g_out column 3 = d sigma; the rgb
-// columns are ignored): save from the sigma-only training forward
-NR_API int NR_X3_NAME(nr_mlp_bwd_sigma)(const void* packed_bwd, const float* head,
-                               const float* out, const float* g_out, const float* save,
-                               int64_t n, float* grad_ws, void* stream) {
-    return bwd3_launch("nr_mlp_bwd_sigma_x3", true, packed_bwd, head, out, g_out, save, n,
-                       grad_ws, stream);
-}
-
-#if !NR_BF1
-// the same over the samples nr_active_samples listed (samples / count on the
-// device), packed: grad_ws holds position q's rows at q -- only the matching
-// nr_wgrad*_active entry point (same list) may consume it
-NR_API int NR_X3_NAME(nr_mlp_bwd_active)(const void* packed_bwd, const float* head,
-                                         const float* out, const float* g_out, const float* save,
-                                         int64_t n, float* grad_ws, const int32_t* samples,
-                                         const int32_t* count, void* stream) {
-    NR_REQUIRE(samples && count, "nr_mlp_bwd_active: null sample list");
-    return bwd3_launch("nr_mlp_bwd_active", false, packed_bwd, head, out, g_out, save, n, grad_ws,
-                       stream, samples, count);
-}
-NR_API int NR_X3_NAME(nr_mlp_bwd_sigma_active)(const void* packed_bwd, const float* head,
-                                               const float* out, const float* g_out,
-                                               const float* save, int64_t n, float* grad_ws,
-                                               const int32_t* samples, const int32_t* count,
-                                               void* stream) {
-    NR_REQUIRE(samples && count, "nr_mlp_bwd_sigma_active: null sample list");
-    return bwd3_launch("nr_mlp_bwd_sigma_active", true, packed_bwd, head, out, g_out, save, n,
-                       grad_ws, stream, samples, count);
-}
-// the deferred save: the same list over a save buffer nr_mlp_fwd_listed* wrote
-// by position (masks read by position, g_out / out gathered by the list)
-NR_API int NR_X3_NAME(nr_mlp_bwd_listed)(const void* packed_bwd, const float* head,
-                                         const float* out, const float* g_out, const float* save,
-                                         int64_t n, float* grad_ws, const int32_t* samples,
-                                         const int32_t* count, void* stream) {
-    NR_REQUIRE(samples && count, "nr_mlp_bwd_listed: null sample list");
-    return bwd3_launch("nr_mlp_bwd_listed", false, packed_bwd, head, out, g_out, save, n, grad_ws,
-                       stream, samples, count, true);
-}
-NR_API int NR_X3_NAME(nr_mlp_bwd_sigma_listed)(const void* packed_bwd, const float* head,
-                                               const float* out, const float* g_out,
-                                               const float* save, int64_t n, float* grad_ws,
-                                               const int32_t* samples, const int32_t* count,
-                                               void* stream) {
-    NR_REQUIRE(samples && count, "nr_mlp_bwd_sigma_listed: null sample list");
-    return bwd3_launch("nr_mlp_bwd_sigma_listed", true, packed_bwd, head, out, g_out, save, n,
-                       grad_ws, stream, samples, count, true);
-}
+// (listed in the order that keeps the kernels' places in the code object)
+#if !NR_BF1     // no sample lists for the bf16 variant
+NR_BWD3_LIST_ENTRY(nr_mlp_bwd_sigma_listed, true, 2)
+NR_BWD3_LIST_ENTRY(nr_mlp_bwd_listed, false, 2)
+NR_BWD3_LIST_ENTRY(nr_mlp_bwd_sigma_active, true, 1)
+NR_BWD3_LIST_ENTRY(nr_mlp_bwd_active, false, 1)
 #endif
+NR_BWD3_ENTRY(nr_mlp_bwd_sigma, true)
+NR_BWD3_ENTRY(nr_mlp_bwd, false)

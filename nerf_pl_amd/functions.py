@@ -5,7 +5,8 @@ needs a gradient); backward = fused data-gradient chain (``nr_mlp_bwd``) then
 the grouped split-K weight-gradient GEMM (``nr_wgrad``), returning one gradient
 per ``NeRF`` parameter (views into one flat buffer, named_parameters order).
 
-``_Composite``: volume compositing forward/backward (``nr_composite_*``).
+``_Composite``: volume compositing forward/backward (``nr_composite_*``, with
+the disparity map ``nr_composite_disp_*``).
 """
 from __future__ import annotations
 
@@ -190,75 +191,38 @@ class _FusedMLP(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_out):
+        """The data gradient, then the weight gradient, in one of three modes:
+        "" every sample, "_active" the listed samples gathered from the
+        forward's save, "_listed" the deferred save -- the training forward
+        re-run over the listed samples (activations saved by position), then
+        both gradients over those positions."""
         if ctx.defer:
-            return _FusedMLP._backward_deferred(ctx, g_out)
-        out, save, packed_f, packed_b, flat = ctx.saved_tensors[:5]
-        n = out.shape[0]
+            out, rays, z, packed_f, packed_b, flat = ctx.saved_tensors[:6]
+            n, mode = z.numel(), "_listed"
+        else:
+            out, save, packed_f, packed_b, flat = ctx.saved_tensors[:5]
+            n = out.shape[0]
+            mode = "_active" if ACTIVE_SAMPLES and ops.arith_of(packed_b) in ACTIVE_ARITHS else ""
         dev = out.device
-        if ctx.sigma_only:
-            g4 = torch.zeros(n, 4, device=dev)
-            g4[:, 3:4] = g_out
-            g_out = g4
-        grad_ws = torch.empty(ops.n_blocks(n) * ops.GRAD_PER_BLOCK, device=dev)
-        g_out = g_out.contiguous()
-        sfx = "_sigma" if ctx.so_kernels else ""
-        st = stream_of(dev)
-        active = ()
-        if ACTIVE_SAMPLES and ops.arith_of(packed_b) in ACTIVE_ARITHS:
-            # the samples with a nonzero output gradient, ascending (int32 [0, n)),
-            # their count ([n]) and the compaction's scratch
-            sl = torch.empty(n + 1 + 2 * ((n + 31) // 32), dtype=torch.int32, device=dev)
-            call("nr_active_samples", g_out.data_ptr(), n, sl.data_ptr(), sl.data_ptr() + 4 * n,
-                 sl.data_ptr() + 4 * (n + 1), st)
-            active = (sl.data_ptr(), sl.data_ptr() + 4 * n)
-            if ACTIVE_LOG is not None:
-                ACTIVE_LOG.append((sl, n))
-            if ctx.model is not None:
-                _note_listed(ctx.model, ctx.sigma_only, sl[n:n + 1], n)
-            sfx += "_active"
-        call(ops.entry("nr_mlp_bwd" + sfx, packed_b), packed_b.data_ptr(), ops.head_ptr(packed_f),
-             out.data_ptr(), g_out.data_ptr(), save.data_ptr(), n, grad_ws.data_ptr(), *active, st)
-        gflat = torch.empty(packing.N_PARAMS, device=dev)
-        ws = _wgrad_workspace(dev.index, int(st))
-        call(ops.entry("nr_wgrad" + sfx, packed_b), save.data_ptr(), grad_ws.data_ptr(), n,
-             ws.data_ptr(), gflat.data_ptr(), *active, st)
-        if not ctx.so_kernels:
-            _dir_feat(flat, gflat, st)
-        if _DEBUG is not None:
-            _DEBUG.update(save=save, grad_ws=grad_ws, g_out=g_out, gflat=gflat, n=n)
-            _DEBUG.setdefault("g_outs", []).append(g_out)
-        return (None,) * 6 + _param_grads(gflat, ctx.sigma_only)
-
-    @staticmethod
-    def _backward_deferred(ctx, g_out):
-        """The deferred save's backward: the sample list of g_out, the training
-        forward re-run over the listed samples (activations saved by position),
-        then the data and weight gradients over those positions."""
-        out, rays, z, packed_f, packed_b, flat = ctx.saved_tensors[:6]
-        n = z.numel()
-        dev = z.device
-        if g_out.shape[1] == 1:            # a sigma-only graph's d sigma
+        if ctx.sigma_only:                 # a sigma-only graph's d sigma
             g4 = torch.zeros(n, 4, device=dev)
             g4[:, 3:4] = g_out
             g_out = g4
         g_out = g_out.contiguous()
         if out.shape[1] != 4:              # the rgb rows only feed the rgb head's backward
             out = g_out
-        st = stream_of(dev)
-        sl = torch.empty(n + 1 + 2 * ((n + 31) // 32), dtype=torch.int32, device=dev)
-        call("nr_active_samples", g_out.data_ptr(), n, sl.data_ptr(), sl.data_ptr() + 4 * n,
-             sl.data_ptr() + 4 * (n + 1), st)
-        lst = (sl.data_ptr(), sl.data_ptr() + 4 * n)
-        if ACTIVE_LOG is not None:
-            ACTIVE_LOG.append((sl, n))
-        if ctx.model is not None:
-            _note_listed(ctx.model, ctx.sigma_only, sl[n:n + 1], n)
         so = ctx.so_kernels
-        save = torch.empty(ops.save_floats(n), device=dev)
-        call(ops.entry("nr_mlp_fwd_listed", packed_f), packed_f.data_ptr(), rays.data_ptr(),
-             z.data_ptr(), n, int(ctx.spr), int(so), save.data_ptr(), *lst, st)
+        sfx = ("_sigma" if so else "") + mode
+        st = stream_of(dev)
+        lst = ()
+        if mode:
+            sl = _sample_list(ctx, g_out, n, st)
+            lst = (sl.data_ptr(), sl.data_ptr() + 4 * n)
+        if ctx.defer:
+            save = torch.empty(ops.save_floats(n), device=dev)
+            call(ops.entry("nr_mlp_fwd_listed", packed_f), packed_f.data_ptr(), rays.data_ptr(),
+                 z.data_ptr(), n, int(ctx.spr), int(so), save.data_ptr(), *lst, st)
         grad_ws = torch.empty(ops.n_blocks(n) * ops.GRAD_PER_BLOCK, device=dev)
-        sfx = "_sigma_listed" if so else "_listed"
         call(ops.entry("nr_mlp_bwd" + sfx, packed_b), packed_b.data_ptr(), ops.head_ptr(packed_f),
              out.data_ptr(), g_out.data_ptr(), save.data_ptr(), n, grad_ws.data_ptr(), *lst, st)
         gflat = torch.empty(packing.N_PARAMS, device=dev)
@@ -267,7 +231,23 @@ class _FusedMLP(torch.autograd.Function):
              ws.data_ptr(), gflat.data_ptr(), *lst, st)
         if not so:
             _dir_feat(flat, gflat, st)
+        if _DEBUG is not None:
+            _DEBUG.update(save=save, grad_ws=grad_ws, g_out=g_out, gflat=gflat, n=n)
+            _DEBUG.setdefault("g_outs", []).append(g_out)
         return (None,) * 6 + _param_grads(gflat, ctx.sigma_only)
+
+
+def _sample_list(ctx, g_out, n, st):
+    """The samples with a nonzero output gradient, ascending (int32 [0, n)),
+    their count ([n]) and the compaction's scratch, in one buffer."""
+    sl = torch.empty(n + 1 + 2 * ((n + 31) // 32), dtype=torch.int32, device=g_out.device)
+    call("nr_active_samples", g_out.data_ptr(), n, sl.data_ptr(), sl.data_ptr() + 4 * n,
+         sl.data_ptr() + 4 * (n + 1), st)
+    if ACTIVE_LOG is not None:
+        ACTIVE_LOG.append((sl, n))
+    if ctx.model is not None:
+        _note_listed(ctx.model, ctx.sigma_only, sl[n:n + 1], n)
+    return sl
 
 
 def _dir_feat(flat, gflat, st):
@@ -307,62 +287,42 @@ def mlp_apply(model, *, rays=None, z=None, spr=0, x=None, sigma_only=False):
 
 
 class _Composite(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, raw, z, rays, noise, noise_std, seed, stream, white_back):
-        rgb, depth, opac, w = ops.composite_forward(raw, z, rays, noise, noise_std, seed, stream,
-                                                    white_back)
-        ctx.save_for_backward(raw, z, rays, noise if noise is not None else torch.empty(0))
-        ctx.cfg = (noise is not None, noise_std, seed, stream, white_back)
-        ctx.mark_non_differentiable(w)
-        # unused outputs (depth, opacity in the training loss) reach backward as
-        # None -- the kernel treats a null gradient as zero -- instead of as
-        # zero tensors autograd would fill with one launch each
-        ctx.set_materialize_grads(False)
-        return rgb, depth, opac, w
+    """Volume compositing: outputs (rgb, depth, opacity, weights), or with
+    ``disp`` (rgb, depth, opacity, disp, weights) -- the disparity map of
+    rendering_rgb_sm.py:197 (``nr_composite_disp_*``)."""
 
     @staticmethod
-    def backward(ctx, g_rgb, g_depth, g_opac, g_w):   # noqa: ARG004 -- weights not differentiable
-        raw, z, rays, noise = ctx.saved_tensors
-        has_noise, noise_std, seed, stream, white_back = ctx.cfg
-        g_raw = ops.composite_backward(raw, z, rays, noise if has_noise else None, noise_std, seed,
-                                       stream, white_back, g_rgb, g_depth, g_opac)
-        return g_raw, None, None, None, None, None, None, None
-
-
-def composite_apply(raw, z, rays, noise, noise_std, seed, stream, white_back):
-    if torch.is_grad_enabled() and raw.requires_grad:
-        return _Composite.apply(raw, z, rays, noise, noise_std, seed, stream, white_back)
-    return ops.composite_forward(raw, z, rays, noise, noise_std, seed, stream, white_back)
-
-
-class _CompositeDisp(torch.autograd.Function):
-    """_Composite with the disparity map of rendering_rgb_sm.py:197
-    (``nr_composite_disp_*``): outputs (rgb, depth, opacity, disp, weights)."""
-
-    @staticmethod
-    def forward(ctx, raw, z, rays, noise, noise_std, seed, stream, white_back):
-        rgb, depth, opac, disp, w = ops.composite_disp_forward(raw, z, rays, noise, noise_std,
-                                                               seed, stream, white_back)
+    def forward(ctx, raw, z, rays, noise, noise_std, seed, stream, white_back, disp):
+        outs = ops.composite_forward(raw, z, rays, noise, noise_std, seed, stream, white_back,
+                                     disp=disp)
+        # the disparity's backward reads the forward's depth and opacity
         ctx.save_for_backward(raw, z, rays, noise if noise is not None else torch.empty(0),
-                              depth, opac)
-        ctx.cfg = (noise is not None, noise_std, seed, stream, white_back)
-        ctx.mark_non_differentiable(w)
-        # as in _Composite; an unused disp (the joint trainer's loss reads rgb
-        # and, through the shadow map, depth) costs the backward nothing
+                              *(outs[1:3] if disp else ()))
+        ctx.cfg = (noise is not None, noise_std, seed, stream, white_back, disp)
+        ctx.mark_non_differentiable(outs[-1])
+        # unused outputs (depth, opacity in the training loss; disp in the joint
+        # trainer's) reach backward as None -- the kernel treats a null gradient
+        # as zero -- instead of as zero tensors autograd would fill with one
+        # launch each
         ctx.set_materialize_grads(False)
-        return rgb, depth, opac, disp, w
+        return outs
 
     @staticmethod
-    def backward(ctx, g_rgb, g_depth, g_opac, g_disp, g_w):   # noqa: ARG004
-        raw, z, rays, noise, depth, opac = ctx.saved_tensors
-        has_noise, noise_std, seed, stream, white_back = ctx.cfg
-        g_raw = ops.composite_disp_backward(raw, z, rays, noise if has_noise else None, noise_std,
-                                            seed, stream, white_back, g_rgb, g_depth, g_opac,
-                                            g_disp, depth, opac)
-        return g_raw, None, None, None, None, None, None, None
+    def backward(ctx, *g):   # (g_rgb, g_depth, g_opac[, g_disp], g_w): weights not differentiable
+        raw, z, rays, noise = ctx.saved_tensors[:4]
+        has_noise, noise_std, seed, stream, white_back, disp = ctx.cfg
+        g_raw = ops.composite_backward(raw, z, rays, noise if has_noise else None, noise_std, seed,
+                                       stream, white_back, *g[:-1], *ctx.saved_tensors[4:],
+                                       disp=disp)
+        return (g_raw,) + (None,) * 8
 
 
-def composite_disp_apply(raw, z, rays, noise, noise_std, seed, stream, white_back):
+def composite_apply(raw, z, rays, noise, noise_std, seed, stream, white_back, disp=False):
     if torch.is_grad_enabled() and raw.requires_grad:
-        return _CompositeDisp.apply(raw, z, rays, noise, noise_std, seed, stream, white_back)
-    return ops.composite_disp_forward(raw, z, rays, noise, noise_std, seed, stream, white_back)
+        return _Composite.apply(raw, z, rays, noise, noise_std, seed, stream, white_back, disp)
+    return ops.composite_forward(raw, z, rays, noise, noise_std, seed, stream, white_back,
+                                 disp=disp)
+
+
+def composite_disp_apply(*args):
+    return composite_apply(*args, disp=True)

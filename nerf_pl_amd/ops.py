@@ -255,9 +255,13 @@ def coarse_z(rays, n_samples, use_disp, perturb, u=None, seed=0):
 
 
 def composite_forward(raw, z, rays, noise, noise_std, seed, rng_stream, white_back,
-                      weights_only=False):
+                      weights_only=False, disp=False):
     """raw (R*S, 4) [rgb, sigma] or (R*S, 1) sigma (then rgb is None: the
-    sigma-only render of rendering_shadows.py:164-198)."""
+    sigma-only render of rendering_shadows.py:164-198) -> (rgb, depth, opacity,
+    weights); with ``disp`` also disp = 1 / max(1e-10, depth / opacity)
+    (rendering_rgb_sm.py:197): (rgb, depth, opacity, disp, weights)."""
+    if disp and weights_only:
+        raise ValueError("composite_forward: weights_only produces no disparity map")
     z = _dev(z, "z")
     n_rays, S = z.shape
     stride = raw.shape[-1]
@@ -266,58 +270,33 @@ def composite_forward(raw, z, rays, noise, noise_std, seed, rng_stream, white_ba
     w = torch.empty(n_rays, S, device=dev)
     rgb = None if weights_only or stride < 4 else torch.empty(n_rays, 3, device=dev)
     depth = None if weights_only else torch.empty(n_rays, device=dev)
-    call("nr_composite_fwd", ptr(raw), stride, stride - 1, ptr(z), ptr(rays), ptr(noise),
-         float(noise_std), seed, rng_stream, n_rays, S, int(white_back), int(weights_only),
-         ptr(rgb), ptr(depth), ptr(opac), ptr(w), stream_of(dev))
-    return rgb, depth, opac, w
+    dmap = (torch.empty(n_rays, device=dev),) if disp else ()
+    call("nr_composite_disp_fwd" if disp else "nr_composite_fwd", ptr(raw), stride, stride - 1,
+         ptr(z), ptr(rays), ptr(noise), float(noise_std), seed, rng_stream, n_rays, S,
+         int(white_back), int(weights_only), ptr(rgb), ptr(depth), ptr(opac), *map(ptr, dmap),
+         ptr(w), stream_of(dev))
+    return (rgb, depth, opac) + dmap + (w,)
 
 
 def composite_backward(raw, z, rays, noise, noise_std, seed, rng_stream, white_back,
-                       g_rgb, g_depth, g_opacity):
+                       g_rgb, g_depth, g_opacity, g_disp=None, depth=None, opacity=None,
+                       disp=False):
+    """With ``disp`` also the disparity's gradient; ``depth`` / ``opacity`` are
+    composite_forward's outputs (read only when ``g_disp`` is given)."""
     n_rays, S = z.shape
     stride = raw.shape[-1]
     g_raw = torch.empty(n_rays * S, stride, device=z.device)
-    call("nr_composite_bwd", ptr(raw), stride, stride - 1, ptr(z), ptr(rays), ptr(noise), float(noise_std), seed,
-         rng_stream, n_rays, S, int(white_back),
-         ptr(None if g_rgb is None else g_rgb.contiguous()),
-         ptr(None if g_depth is None else g_depth.contiguous()),
-         ptr(None if g_opacity is None else g_opacity.contiguous()), ptr(g_raw),
-         stream_of(z.device))
+    grads = (g_rgb, g_depth, g_opacity) + ((g_disp, depth, opacity) if disp else ())
+    call("nr_composite_disp_bwd" if disp else "nr_composite_bwd", ptr(raw), stride, stride - 1,
+         ptr(z), ptr(rays), ptr(noise), float(noise_std), seed, rng_stream, n_rays, S,
+         int(white_back), *(ptr(None if t is None else t.contiguous()) for t in grads),
+         ptr(g_raw), stream_of(z.device))
     return g_raw
 
 
-def composite_disp_forward(raw, z, rays, noise, noise_std, seed, rng_stream, white_back):
-    """composite_forward plus disp = 1 / max(1e-10, depth / opacity)
-    (rendering_rgb_sm.py:197): (rgb, depth, opacity, disp, weights)."""
-    z = _dev(z, "z")
-    n_rays, S = z.shape
-    stride = raw.shape[-1]
-    dev = z.device
-    opac = torch.empty(n_rays, device=dev)
-    w = torch.empty(n_rays, S, device=dev)
-    rgb = None if stride < 4 else torch.empty(n_rays, 3, device=dev)
-    depth = torch.empty(n_rays, device=dev)
-    disp = torch.empty(n_rays, device=dev)
-    call("nr_composite_disp_fwd", ptr(raw), stride, stride - 1, ptr(z), ptr(rays), ptr(noise),
-         float(noise_std), seed, rng_stream, n_rays, S, int(white_back), 0, ptr(rgb), ptr(depth),
-         ptr(opac), ptr(disp), ptr(w), stream_of(dev))
-    return rgb, depth, opac, disp, w
-
-
-def composite_disp_backward(raw, z, rays, noise, noise_std, seed, rng_stream, white_back,
-                            g_rgb, g_depth, g_opacity, g_disp=None, depth=None, opacity=None):
-    """composite_backward with the disparity's gradient; ``depth`` / ``opacity``
-    are composite_disp_forward's outputs (read only when ``g_disp`` is given)."""
-    n_rays, S = z.shape
-    stride = raw.shape[-1]
-    g_raw = torch.empty(n_rays * S, stride, device=z.device)
-
-    def c(t):
-        return ptr(None if t is None else t.contiguous())
-    call("nr_composite_disp_bwd", ptr(raw), stride, stride - 1, ptr(z), ptr(rays), ptr(noise),
-         float(noise_std), seed, rng_stream, n_rays, S, int(white_back), c(g_rgb), c(g_depth),
-         c(g_opacity), c(g_disp), c(depth), c(opacity), ptr(g_raw), stream_of(z.device))
-    return g_raw
+# the disparity forms under their own names (rendering_rgb_sm.py:197)
+composite_disp_forward = functools.partial(composite_forward, disp=True)
+composite_disp_backward = functools.partial(composite_backward, disp=True)
 
 
 def sample_pdf(weights, rays, n_importance, u=None, jitter=None, seed=0, z_coarse=None,

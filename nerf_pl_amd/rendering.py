@@ -28,7 +28,7 @@ import os
 import torch
 
 from . import ops
-from .functions import composite_apply, composite_disp_apply, mlp_apply
+from .functions import composite_apply, mlp_apply
 from .rng import (STREAM_JITTER, STREAM_NOISE_COARSE, STREAM_NOISE_FINE, STREAM_PERTURB,
                   STREAM_U, PhiloxRNG, TorchRNG)
 
@@ -126,11 +126,16 @@ def render_rays(models, embeddings, rays, N_samples=64, use_disp=False, perturb=
 
 
 def _render_rays(models, embeddings, rays, N_samples, use_disp, perturb, noise_std, N_importance,
-                 chunk, white_back, test_time, rng, _capture, disp=False, depth_only=False):
+                 chunk, white_back, test_time, rng, _capture, disp=False, depth_only=False,
+                 pipelined=True, empty_ok=False):
     """The render behind ``rendering.render_rays`` and, with ``disp``,
     ``rendering_rgb_sm.render_rays`` (the same function plus ``disp_map_*``,
     rendering_rgb_sm.py:197, 253, 276).  ``depth_only``: every MLP call is the
-    sigma-only graph and no ``rgb_*`` is produced."""
+    sigma-only graph and no ``rgb_*`` is produced.  ``rendering_shadows.render_rays``
+    is this render with ``depth_only`` and two switches: ``pipelined=False``
+    keeps the fine pass on the caller's stream and leaves ``BEFORE_FINE``
+    alone; ``empty_ok`` renders an empty batch to empty maps (a rank's slice in
+    ``render_rays_sharded``) where the reference's ``rendering.py`` raises."""
     if isinstance(rays, torch.Tensor) and rays.device.type == "cpu":
         if depth_only:
             raise NotImplementedError("nerf_pl_amd.render_rays: depth_only needs a HIP-device batch")
@@ -153,7 +158,7 @@ def _render_rays(models, embeddings, rays, N_samples, use_disp, perturb, noise_s
     rays = ops._dev(rays, "rays", 8)
     dev = rays.device
     n_rays = rays.shape[0]
-    if n_rays == 0:
+    if n_rays == 0 and not empty_ok:
         # the reference fails here too: its chunk loop yields no chunk and
         # torch.cat([]) raises (rendering.py:150-161)
         raise ValueError("nerf_pl_amd.render_rays: empty ray batch (the reference's "
@@ -163,18 +168,14 @@ def _render_rays(models, embeddings, rays, N_samples, use_disp, perturb, noise_s
 
     def composite(result, level, raw, z, noise, stream):
         """compositing of one pass into ``result``; returns the weights"""
-        if disp:
-            rgb, depth, opac, dmap, w = composite_disp_apply(raw, z, rays, noise, noise_std, seed,
-                                                             stream, white_back)
-        else:
-            rgb, depth, opac, w = composite_apply(raw, z, rays, noise, noise_std, seed, stream,
-                                                  white_back)
+        rgb, depth, opac, *dmap, w = composite_apply(raw, z, rays, noise, noise_std, seed, stream,
+                                                     white_back, disp)
         if rgb is not None:
             result["rgb_" + level] = rgb
         result["depth_" + level] = depth
         result["opacity_" + level] = opac
         if disp:
-            result["disp_map_" + level] = dmap
+            result["disp_map_" + level] = dmap[0]
         return w
 
     # stratified coarse depths (rendering.py:216-232)
@@ -215,9 +216,9 @@ def _render_rays(models, embeddings, rays, N_samples, use_disp, perturb, noise_s
             w = composite(fine, "fine", raw_f, z_f, noise_f, STREAM_NOISE_FINE)
             return tuple(fine.values()) + (w,)
 
-        while BEFORE_FINE:
+        while pipelined and BEFORE_FINE:
             BEFORE_FINE.pop(0)()
-        if FINE_STREAM and torch.is_grad_enabled() and any(
+        if pipelined and FINE_STREAM and torch.is_grad_enabled() and any(
                 p.requires_grad for p in models[1].parameters()):
             main = torch.cuda.current_stream(dev)
             side = _side_stream(dev.index)

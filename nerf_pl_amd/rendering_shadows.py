@@ -26,9 +26,7 @@ import torch
 from . import efficient_shadow_mapping as _esm
 from . import ops
 from .efficient_shadow_mapping import EPSILON, _cam
-from .functions import composite_apply, mlp_apply
-from .rendering import _check_embeddings
-from .rng import STREAM_NOISE_COARSE, STREAM_NOISE_FINE, PhiloxRNG
+from .rendering import _check_embeddings, _render_rays
 
 __all__ = ["render_rays", "render_rays_sharded", "efficient_sm"]
 
@@ -42,50 +40,22 @@ def _disp(depth, opac):
 def render_rays(models, embeddings, rays, N_samples=64, use_disp=False, perturb=0, noise_std=1,
                 N_importance=0, chunk=1024 * 32, white_back=False, test_time=False,
                 were_gradients_computed=True, *, rng=None, _capture=None):
-    del chunk, white_back, were_gradients_computed
+    """``rendering._render_rays`` on the sigma-only graph, everything on the
+    caller's stream, plus ``disp_map_*`` in torch (its autograd rounds unlike
+    ``nr_composite_disp_bwd``'s).  Fused kernels only: a host batch or a
+    non-default model raises here."""
+    del white_back, were_gradients_computed
     _check_embeddings(embeddings, models)
     rays = ops._dev(rays, "rays", 8)
-    dev = rays.device
-    n_rays = rays.shape[0]
-    rng = PhiloxRNG() if rng is None else rng
-    seed = rng.seed
-
-    u1 = rng.rand((n_rays, N_samples), dev) if perturb > 0 else None
-    z_c = ops.coarse_z(rays, N_samples, use_disp, perturb, u=u1, seed=seed)
-    noise_c = rng.randn((n_rays, N_samples), dev)
-    cap = _capture if _capture is not None else {}
-    cap["z_coarse"] = z_c
+    res = _render_rays(models, embeddings, rays, N_samples, use_disp, perturb, noise_std,
+                       N_importance, chunk, False, test_time, rng, _capture, depth_only=True,
+                       pipelined=False, empty_ok=True)
     result = {}
-    if test_time:
-        with torch.no_grad():
-            sig = mlp_apply(models[0], rays=rays, z=z_c, spr=N_samples, sigma_only=True)
-            _, _, opac_c, w_c = ops.composite_forward(sig, z_c, rays, noise_c, noise_std, seed,
-                                                      STREAM_NOISE_COARSE, False,
-                                                      weights_only=True)
-        result["opacity_coarse"] = opac_c
-    else:
-        sig = mlp_apply(models[0], rays=rays, z=z_c, spr=N_samples, sigma_only=True)
-        _, depth_c, opac_c, w_c = composite_apply(sig, z_c, rays, noise_c, noise_std, seed,
-                                                  STREAM_NOISE_COARSE, False)
-        result["depth_coarse"] = depth_c
-        result["opacity_coarse"] = opac_c
-        result["disp_map_coarse"] = _disp(depth_c, opac_c)
-
-    if N_importance > 0:
-        u = rng.rand((n_rays, N_importance), dev)
-        jit = rng.rand((n_rays, N_importance), dev)
-        _, z_f = ops.sample_pdf(w_c.detach(), rays, N_importance, u=u, jitter=jit, seed=seed,
-                                z_coarse=z_c, merge=True)
-        cap["weights_coarse"] = w_c
-        cap["z_fine"] = z_f
-        s_f = N_samples + N_importance
-        noise_f = rng.randn((n_rays, s_f), dev)
-        sig_f = mlp_apply(models[1], rays=rays, z=z_f, spr=s_f, sigma_only=True)
-        _, depth_f, opac_f, _ = composite_apply(sig_f, z_f, rays, noise_f, noise_std, seed,
-                                                STREAM_NOISE_FINE, False)
-        result["depth_fine"] = depth_f
-        result["opacity_fine"] = opac_f
-        result["disp_map_fine"] = _disp(depth_f, opac_f)
+    for key, v in res.items():          # depth, opacity[, disp_map] per level
+        result[key] = v
+        level = key.partition("_")[2]
+        if key.startswith("opacity_") and "depth_" + level in res:
+            result["disp_map_" + level] = _disp(res["depth_" + level], v)
     return result
 
 

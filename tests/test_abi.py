@@ -1,5 +1,6 @@
 """CPU-side checks of the C-ABI library: it loads, exports every symbol the
 header declares, and its layout constants agree with the Python packing."""
+import ctypes
 import os
 import re
 
@@ -22,6 +23,47 @@ def test_library_exports_header_symbols():
     missing = [s for s in syms if getattr(L, s, None) is None]
     assert not missing, missing
     assert set(syms) == set(_lib.SIGNATURES), set(syms) ^ set(_lib.SIGNATURES)
+
+
+_CTYPES = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "uint64_t": ctypes.c_uint64,
+           "float": ctypes.c_float, "double": ctypes.c_double}
+
+
+def _header_prototypes():
+    """name -> (return ctype, [argument ctypes]) of every prototype of the
+    header, comments stripped; any pointer is a c_void_p (a returned
+    ``const char*`` a c_char_p)"""
+    txt = open(os.path.join(REPO, "include", "nerf_pl_amd.h")).read()
+    txt = re.sub(r"/\*.*?\*/", " ", txt, flags=re.S)
+    txt = re.sub(r"//[^\n]*", " ", txt)
+
+    def ctype(decl, ret=False):
+        if "*" in decl:
+            return ctypes.c_char_p if ret else ctypes.c_void_p
+        # the type is the first word: a parameter's name follows it
+        return _CTYPES[[w for w in decl.split() if w not in ("const", "NR_EXPORT")][0]]
+
+    protos = {}
+    for ret, name, args in re.findall(r"([\w\s\*]+?)\b(nr_\w+)\s*\(([^)]*)\)\s*;", txt):
+        assert name not in protos, name
+        args = args.strip()
+        argtypes = [] if args in ("", "void") else [ctype(a) for a in args.split(",")]
+        protos[name] = (ctype(ret, ret=True), argtypes)
+    return protos
+
+
+def test_signatures_match_header_types():
+    """_lib.SIGNATURES / _RESTYPES against the header, argument by argument: a
+    wrong row would truncate a 64-bit argument (or widen a 32-bit one) at the
+    call boundary without any error."""
+    from nerf_pl_amd import _lib
+    protos = _header_prototypes()
+    assert len(protos) == 90
+    assert set(protos) == set(_lib.SIGNATURES), set(protos) ^ set(_lib.SIGNATURES)
+    bad = {n: (ret, args) for n, (ret, args) in protos.items()
+           if args != list(_lib.SIGNATURES[n]) or ret != _lib._RESTYPES.get(n, ctypes.c_int)}
+    assert not bad, bad
+    assert set(_lib._RESTYPES) <= set(protos)
 
 
 def test_layout_constants_match_packing():
