@@ -19,7 +19,9 @@
 // destination maps, the reductions, the launch plan and the entry points.
 #include <stdlib.h>
 
-#include "wgrad_common.h"   // task / launch structs, split-K and fusion constants
+#include <type_traits>
+
+#include "wgrad_common.h"   // task / launch structs, the workgroup prologue; wgrad_plan.h: the launch plan
 #include "wgrad_f32.h"      // wgrad_kernel: exact fp32 (base object only)
 #include "wgrad3.h"         // wgrad3_kernel: register-staged split operands; bf16: wgrad_b1.h
 #include "wgrad4.h"         // wgrad4_kernel: f16x3 LDS-DMA (f16x3 object only)
@@ -133,6 +135,9 @@ __global__ void wgrad_reduce_kernel(WgArgs a, float* __restrict__ grad) {
     grad[dst] = s;
 }
 
+// the slab workspace every launch gets: the largest plan of any arithmetic and path
+constexpr int64_t kWorkspaceFloats = wgrad_plan_max_floats();
+
 }  // namespace
 
 #if NR_X3_BASE_OBJECT
@@ -189,12 +194,31 @@ NR_API int nr_wgrad_dir_feat(const float* params, float* grad_flat, void* stream
 
 NR_API int64_t nr_wgrad_workspace_bytes(int64_t n) {
     (void)n;
-    // upper bound of sum_t G_t * (M_t N_t + M_t) for the task list below
-    return (int64_t)(3 * kTargetWGMax + kTasks) * (256 * 256 + 256) * sizeof(float);
+    return kWorkspaceFloats * (int64_t)sizeof(float);
 }
 #endif
 
 namespace {
+// this object's split arithmetic
+constexpr WgArith kArith = NR_F16 ? kArithF16x3 : NR_BF1 ? kArithBf16 : kArithBf16x6;
+static_assert(kArith.split && kArith.nprod == x3::kNProd && kArith.fuse == kFuse &&
+              kArith.w4 == (NR_F16 == 1) && kArith.lists == !NR_BF1, "wgrad_plan.h: this object's row");
+
+// (ga, rows) -> the kernels' template arguments, in the order that keeps the
+// kernels' places in the code object.  bf16 has one kernel: no sample lists,
+// and its segments are bf16 chunks in either graph
+template <class F>
+void with_ga_rows(bool ga, bool rows, F f) {
+    using Y = std::true_type;
+    using N = std::false_type;
+    if constexpr (!NR_BF1) {
+        if (ga && rows) return f(Y{}, Y{});
+        if (ga) return f(Y{}, N{});
+        if (rows) return f(N{}, Y{});
+    }
+    f(N{}, N{});
+}
+
 // slist / scount: the launch covers positions 0 .. *scount of the buffers; with
 // gather the input operands are gathered from sample slist[q] (the *_active
 // entry points), else they were saved by position (the *_listed ones)
@@ -215,14 +239,19 @@ int wgrad_launch(bool x3, bool sigma_only, const float* save, const float* grad_
     }
     const int64_t nb = (n + 31) / 32;          // blocks holding samples (the work)
     const int64_t nbp = nr_blocks_pad(n);      // segment stride of the buffers
-    float* SV = const_cast<float*>(save);
-    float* GD = const_cast<float*>(grad_ws);
-    auto acc = [](float* p, int w) { return WgSeg{p, SEG_ACC, w}; };
-    const WgSeg pe{SV, SEG_PE, 64}, dpe{SV + nr_sv_dirpe(nbp), SEG_DPE, 32};
-    const WgSeg head{GD + nr_gd_dhead(nbp), SEG_HEAD, 4};
-    auto H = [&](int l) { return acc(SV + nr_sv_h(l, nbp), 256); };
-    auto DZ = [&](int l) { return acc(GD + nr_gd_dz(l, nbp), 256); };
-    // task 10 (dir_encoding's feat columns) reads h8, not xyz_encoding_final's
+    const WgArith& A = x3 ? kArith : kArithF32;
+    // f16x3, full graph: the LDS-DMA weight gradient (wgrad4_kernel).  32-bit
+    // buffer offsets: every segment it reads stays under 2 GiB below 2M samples.
+    // NR_WGRAD_W4=0 in the environment: the register-staged wgrad3_kernel, for
+    // A/B runs and the cross-check test (read per launch)
+    const char* w4_env = getenv("NR_WGRAD_W4");
+    const bool use_w4 = A.w4 && !sigma_only && n < ((int64_t)1 << 21) &&
+                        !(w4_env && atoi(w4_env) == 0);
+    const WgPlan plan = wgrad_plan(A, sigma_only, slist != nullptr, use_w4, nb);
+    NR_REQUIRE(plan.slab_floats <= kWorkspaceFloats,
+               "%s: the launch plan's slabs exceed nr_wgrad_workspace_bytes", name);
+    // the tasks' segments (gradient, input), by task id (wgrad_plan.h kWgShape).
+    // Task 10 (dir_encoding's feat columns) reads h8, not xyz_encoding_final's
     // output: dW = sum dz_dir feat^T = G W_final^T + db_dir b_final^T with
     // G = sum dz_dir h8^T (nerf.py:116, feat = W_final h8 + b_final), so the
     // forward saves no feat.  And task 9 (xyz_encoding_final) launches nothing:
@@ -230,120 +259,29 @@ int wgrad_launch(bool x3, bool sigma_only, const float* save, const float* grad_
     // W_dir[:, :256]^T G (db = W_dir[:, :256]^T db_dir), so the data gradient
     // stores no dfeat either.  nr_wgrad_dir_feat forms both from G
     // (DESIGN.md 13); task 9's entry keeps the id order (its slot: a dummy)
-    const WgSeg hdir = acc(SV + nr_sv_hdir(nbp), 128);
-    const WgSeg dzdir = acc(GD + nr_gd_dzdir(nbp), 128);
-    // (a, b, wm, wn); task order fixes wgrad_dest / wgrad_bias_dest
-    const WgTask tasks[kTasks] = {
-        {DZ(0), pe, 8, 1}, {DZ(1), H(0), 2, 4}, {DZ(2), H(1), 2, 4}, {DZ(3), H(2), 2, 4},
-        {DZ(4), pe, 8, 1}, {DZ(4), H(3), 2, 4}, {DZ(5), H(4), 2, 4}, {DZ(6), H(5), 2, 4},
-        {DZ(7), H(6), 2, 4}, {DZ(0), H(7), 2, 4} /* 9: dummy, no workgroups */,
-        {dzdir, H(7), 2, 4}, {dzdir, dpe, 4, 1},
-        {head, H(7), 1, 8}, {head, hdir, 1, 4},
+    const float* SV = save;
+    const float* GD = grad_ws;
+    auto H = [&](int l) { return SV + nr_sv_h(l, nbp); };
+    auto DZ = [&](int l) { return GD + nr_gd_dz(l, nbp); };
+    const float* pe = SV;
+    const float* dpe = SV + nr_sv_dirpe(nbp);
+    const float* hdir = SV + nr_sv_hdir(nbp);
+    const float* dzdir = GD + nr_gd_dzdir(nbp);
+    const float* head = GD + nr_gd_dhead(nbp);
+    const float* const seg[kTasks][2] = {
+        {DZ(0), pe}, {DZ(1), H(0)}, {DZ(2), H(1)}, {DZ(3), H(2)},
+        {DZ(4), pe}, {DZ(4), H(3)}, {DZ(5), H(4)}, {DZ(6), H(5)},
+        {DZ(7), H(6)}, {DZ(0), H(7)} /* 9: dummy, no workgroups */,
+        {dzdir, H(7)}, {dzdir, dpe}, {head, H(7)}, {head, hdir},
     };
     WgArgs a{};
-    // per-block cost of a task's workgroup, in cycles: the MFMA time of its
-    // busiest SIMD (fp32: 16 k-steps x 64 cycles per tile; bf16x6: 2 x 6 x 32),
-    // or the staging of (M + N) x 32 floats at ~8 B/cycle per CU, plus a fixed
-    // barrier/LDS-store overhead
-    int64_t cost[kTasks], tot = 0;
-    for (int t = 0; t < kTasks; ++t) {
-        const int mt = (tasks[t].a.width / tasks[t].wm + 31) / 32;
-        const int nt = (tasks[t].b.width / tasks[t].wn + 31) / 32;
-        const int64_t per_tile = x3 ? 64 * x3::kNProd : 1024;
-        const int64_t mfma = per_tile * mt * nt * (tasks[t].wm * tasks[t].wn > 4 ? 2 : 1);
-        const int64_t bytes = (int64_t)(tasks[t].a.width + tasks[t].b.width) * 32 * 4;
-        cost[t] = std::max<int64_t>(mfma, bytes / 8) + 512;
-        tot += cost[t];
-    }
-    // dispatch order: the heavy tasks first; the small ones last and split ~3x
-    // finer, so their short workgroups fill the tail of the final round
-    const int64_t heavy = x3 ? 1024 * x3::kNProd : 16384;
-    int order[kTasks], no = 0;
-    for (int pass = 0; pass < 2; ++pass)
-        for (int t = 0; t < kTasks; ++t)
-            if ((cost[t] >= heavy) == (pass == 0)) order[no++] = t;
-    a.wg_start[0] = 0;
-    int64_t slab = 0;
-    // diagnostic: NR_WGRAD_TASKMASK limits the launch to a subset of task ids
-    // (the kernel code is unchanged; gradients of the other tasks are then stale)
-    // gradient operand's stats slot (layout.h NR_STATS) of every task id
-    static const int kStat[kTasks] = {0, 1, 2, 3, 4, 4, 5, 6, 7, 8, 9, 9, 10, 10};
-    static const long long tmask_env =
-        getenv("NR_WGRAD_TASKMASK") ? strtoll(getenv("NR_WGRAD_TASKMASK"), nullptr, 0) : -1;
-    // the sigma-only graph (rendering_shadows.py:167) has no xyz_encoding_final
-    // (task 9), dir_encoding (10, 11) or rgb head (13): their gradients are not
-    // computed (written as 0; the autograd leaves them None)
-    const long long tmask = sigma_only ? (tmask_env & ~((1LL << 9) | (1LL << 10) | (1LL << 11) | (1LL << 13)))
-                                       : tmask_env;
-    // every launch over a sample list -- gathering (*_active) or over buffers
-    // saved by position (*_listed, the deferred save) -- uses the same split-K
-    // partition, so the two give bit-identical sums
-    // f16x3, full graph: the LDS-DMA weight gradient (wgrad4_kernel).  32-bit
-    // buffer offsets: every segment it reads stays under 2 GiB below 2M samples.
-    // NR_WGRAD_W4=0 in the environment: the register-staged wgrad3_kernel, for
-    // A/B runs and the cross-check test (read per launch)
-    const char* w4_env = getenv("NR_WGRAD_W4");
-    const bool use_w4 = NR_F16 && !sigma_only && n < ((int64_t)1 << 21) &&
-                        !(w4_env && atoi(w4_env) == 0);
-    const int64_t target_wg = !slist ? kTargetWG : (use_w4 ? kTargetWGW4 : kTargetWGGather);
-    int64_t gt[kTasks];
-    int pos[kTasks];
     for (int k = 0; k < kTasks; ++k) {
-        const int t = order[k];
-        // the 4-row head tasks' per-block time is mostly fixed cost, not
-        // bytes: always split finer, so they fill the tail of the last round
-        const int split = cost[t] >= heavy && tasks[t].a.kind != SEG_HEAD ? 1 : 3;
-        int64_t g = split * ((target_wg * cost[t] + tot - 1) / tot);
-        gt[t] = std::max<int64_t>(1, std::min<int64_t>(g, nb));
-        if (!((tmask >> t) & 1) || t == 9) gt[t] = 0;   // task 9: nr_wgrad_dir_feat
-        pos[t] = k;
+        const WgPlanTask& p = plan.task[k];
+        const WgShape& s = kWgShape[p.id];
+        a.task[k] = WgTask{{seg[p.id][0], s.ka, s.M}, {seg[p.id][1], s.kb, s.N}, s.wm, s.wn,
+                           p.G, p.slab, p.id, s.stat, p.fuse, p.pa, p.pb};
     }
-    // f16x3: the tasks that read the same saved segment run fused (kFuse,
-    // wgrad3_body's extra operand): the primary's workgroups also compute the
-    // partner's output over the same block ranges into the partner's slabs, so
-    // DZ(4), H(7) and dz_dir (2.5 KB/sample) are read once.  The partner keeps
-    // its slabs and its reduction but launches no workgroups of its own.
-    // (round 5: task 9, xyz_encoding_final = DZ(8) x H(7), launches nothing --
-    // its gradient is W_dir[:, :256]^T G, nr_wgrad_dir_feat -- so the sigma
-    // head pairs with task 10, which reads H(7) too)
-    static const int kFused[2][2] = {{5, 4}, {10, 12}};   // {primary, partner}
-    int partner[kTasks];
-    bool absorbed[kTasks];
-    for (int t = 0; t < kTasks; ++t) { partner[t] = -1; absorbed[t] = false; }
-    if (kFuse && x3 && (tmask_env == -1)) {
-        // launches over a sample list have their own pair set (see target_wg)
-        // (wgrad4_kernel fuses the sigma head into task 10 only)
-        const int fmask = use_w4 ? 2
-                        : (slist && !NR_BF1) ? (kFuseMask & kFuseMaskGather)
-                                             : kFuseMask;
-        for (int i = 0; i < 2; ++i) {
-            if (!((fmask >> i) & 1)) continue;
-            const auto& pr = kFused[i];
-            if (!((tmask >> pr[0]) & 1) || !((tmask >> pr[1]) & 1)) continue;   // both must run
-            gt[pr[1]] = gt[pr[0]] = std::max<int64_t>(1, std::min<int64_t>(
-                (target_wg * (cost[pr[0]] + cost[pr[1]]) + tot - 1) / tot, nb));
-            partner[pr[0]] = pr[1];
-            absorbed[pr[1]] = true;
-        }
-    }
-    for (int k = 0; k < kTasks; ++k) {
-        const int t = order[k];
-        const int64_t g = gt[t];
-        a.task[k] = tasks[t];
-        a.task[k].id = t;
-        a.task[k].stat = kStat[t];
-        a.task[k].G = (int)g;
-        a.task[k].slab = slab;
-        a.task[k].fuse = partner[t] >= 0 ? pos[partner[t]] : -1;
-        // wgrad4_kernel's slab orders: gradient rows 4-interleaved (not the head's), input
-        // columns VB-interleaved (its dispatch below)
-        static const int kW4Pa[kTasks] = {4, 4, 4, 4, 4, 4, 4, 4, 4, 4, 4, 4, 1, 1};
-        static const int kW4Pb[kTasks] = {1, 4, 4, 4, 1, 4, 4, 4, 4, 4, 2, 1, 2, 1};
-        a.task[k].pa = use_w4 ? kW4Pa[t] : 1;
-        a.task[k].pb = use_w4 ? kW4Pb[t] : 1;
-        slab += g * (tasks[t].a.width * tasks[t].b.width + tasks[t].a.width);
-        a.wg_start[k + 1] = a.wg_start[k] + (absorbed[t] ? 0 : (int)g);
-    }
+    for (int k = 0; k <= kTasks; ++k) a.wg_start[k] = plan.wg_start[k];
     a.nb = (int)nb;
     a.n = (int)n;
     a.slab = workspace;
@@ -351,28 +289,24 @@ int wgrad_launch(bool x3, bool sigma_only, const float* save, const float* grad_
     a.stats = NR_F16 ? SV + nr_sv_stats(nbp) : nullptr;
     a.slist = slist;
     a.scount = scount;
+    const int wgs = a.wg_start[kTasks];
+    // GA: gathered inputs; ROWS: the full graph's inputs are sample-major rows
+    // (mlp_fwd.hip ROWS), the sigma-only graph's block-native
+    const bool ga = slist && gather, rows = !sigma_only;
 #if NR_F16
-    stats_reduce_kernel<<<NR_STAT_SEGS, kStatT, 0, st>>>(SV + nr_sv_stats(nbp), (int)nbp);
+    stats_reduce_kernel<<<NR_STAT_SEGS, kStatT, 0, st>>>(const_cast<float*>(SV) + nr_sv_stats(nbp), (int)nbp);
     NR_LAUNCH_CHECK("nr_wgrad_stats");
-    if (use_w4 && slist && gather) wgrad4_kernel<true><<<a.wg_start[kTasks], w4::kT, 0, st>>>(a);
-    else if (use_w4) wgrad4_kernel<false><<<a.wg_start[kTasks], w4::kT, 0, st>>>(a);
-    else if (slist && gather && !sigma_only) wgrad3_kernel<true, true><<<a.wg_start[kTasks], kThreads, 0, st>>>(a);
-    else if (slist && gather) wgrad3_kernel<true, false><<<a.wg_start[kTasks], kThreads, 0, st>>>(a);
-    else if (!sigma_only) wgrad3_kernel<false, true><<<a.wg_start[kTasks], kThreads, 0, st>>>(a);
-    else wgrad3_kernel<false, false><<<a.wg_start[kTasks], kThreads, 0, st>>>(a);
-#elif NR_BF1
-    wgrad3_kernel<false, false><<<a.wg_start[kTasks], kThreads, 0, st>>>(a);
-#else
-    if (x3 && slist && gather && !sigma_only) wgrad3_kernel<true, true><<<a.wg_start[kTasks], kThreads, 0, st>>>(a);
-    else if (x3 && slist && gather) wgrad3_kernel<true, false><<<a.wg_start[kTasks], kThreads, 0, st>>>(a);
-    else if (x3 && !sigma_only) wgrad3_kernel<false, true><<<a.wg_start[kTasks], kThreads, 0, st>>>(a);
-    else if (x3) wgrad3_kernel<false, false><<<a.wg_start[kTasks], kThreads, 0, st>>>(a);
-    // the full graph's inputs are sample-major rows (mlp_fwd.hip ROWS), the
-    // sigma-only graph's block-native
-    else if (slist && gather && !sigma_only) wgrad_kernel<true, true><<<a.wg_start[kTasks], kThreads, 0, st>>>(a);
-    else if (slist && gather) wgrad_kernel<true, false><<<a.wg_start[kTasks], kThreads, 0, st>>>(a);
-    else if (!sigma_only) wgrad_kernel<false, true><<<a.wg_start[kTasks], kThreads, 0, st>>>(a);
-    else wgrad_kernel<false, false><<<a.wg_start[kTasks], kThreads, 0, st>>>(a);
+    if (use_w4 && ga) wgrad4_kernel<true><<<wgs, w4::kT, 0, st>>>(a);
+    else if (use_w4) wgrad4_kernel<false><<<wgs, w4::kT, 0, st>>>(a);
+    else
+#endif
+    if (x3) with_ga_rows(ga, rows, [&](auto GA, auto ROWS) {
+        wgrad3_kernel<GA(), ROWS()><<<wgs, kThreads, 0, st>>>(a);
+    });
+#if NR_X3_BASE_OBJECT
+    else with_ga_rows(ga, rows, [&](auto GA, auto ROWS) {
+        wgrad_kernel<GA(), ROWS()><<<wgs, kThreads, 0, st>>>(a);
+    });
 #endif
     NR_LAUNCH_CHECK("nr_wgrad");
     dim3 rg((256 * 256 + 256 + 255) / 256, kTasks);

@@ -481,17 +481,11 @@ __global__ void __launch_bounds__(kThreads, 1) wgrad3_kernel(WgArgs a) {
 #else
     __shared__ __attribute__((aligned(16))) char lds[w3::kLds];
 #endif
-    int t = 0;
-#pragma unroll 1
-    while (t + 1 < kTasks && (int)blockIdx.x >= a.wg_start[t + 1]) ++t;
-    const int c = blockIdx.x - a.wg_start[t];
-    const WgTask& T = a.task[t];
-    const int nact = wg_nact(a);
-    const int b0 = (int)((int64_t)c * nact / T.G);
-    const int b1 = (int)((int64_t)(c + 1) * nact / T.G);
-    float* slab = a.slab + T.slab + (int64_t)c * (T.a.width * T.b.width + T.a.width);
+    const auto [c, T, b0, b1, slab] = WgWork(a);
     const int fu = __builtin_amdgcn_readfirstlane(T.fuse);
     if constexpr (kFuse) if (fu >= 0) {
+        // the partner's slab (wg_slab spelt out: called here, the compiler computes
+        // it ahead of the task switch and this kernel's schedule moves)
         const WgTask& P = a.task[fu];
         float* xslab = a.slab + P.slab + (int64_t)c * (P.a.width * P.b.width + P.a.width);
 #if NR_BF1

@@ -550,21 +550,10 @@ __device__ __forceinline__ void wgrad4_body(const WgArgs& a, const WgTask& T, in
 template <bool GA>
 __global__ void __launch_bounds__(w4::kT, 1) wgrad4_kernel(WgArgs a) {
     __shared__ __attribute__((aligned(16))) char lds[w4::kLds];
-    int t = 0;
-#pragma unroll 1
-    while (t + 1 < kTasks && (int)blockIdx.x >= a.wg_start[t + 1]) ++t;
-    const int c = blockIdx.x - a.wg_start[t];
-    const WgTask& T = a.task[t];
-    const int nact = wg_nact(a);
-    const int b0 = (int)((int64_t)c * nact / T.G);
-    const int b1 = (int)((int64_t)(c + 1) * nact / T.G);
-    float* slab = a.slab + T.slab + (int64_t)c * (T.a.width * T.b.width + T.a.width);
+    const auto [c, T, b0, b1, slab] = WgWork(a);
     const int fu = __builtin_amdgcn_readfirstlane(T.fuse);
     float* xslab = nullptr;
-    if (fu >= 0) {
-        const WgTask& P = a.task[fu];
-        xslab = a.slab + P.slab + (int64_t)c * (P.a.width * P.b.width + P.a.width);
-    }
+    if (fu >= 0) xslab = wg_slab(a, a.task[fu], c);
     switch (__builtin_amdgcn_readfirstlane(T.id)) {
         case 0: case 4:     // DZ x PE
             wgrad4_body<GA, 256, false, 64, 1, 2, 2>(a, T, b0, b1, lds, slab, xslab); break;

@@ -1,6 +1,8 @@
 // Weight gradient (wgrad.hip): what its kernels share -- the task and launch
-// structs, the split-K and fusion constants, the flat parameter offsets.
+// structs, the workgroup prologue, the flat parameter offsets.  The task table
+// and the split-K and fusion constants: wgrad_plan.h.
 #pragma once
+#include "wgrad_plan.h"
 #include "x3.h"
 
 namespace x3 {
@@ -66,33 +68,13 @@ __device__ __forceinline__ void mfma_xp_multi(const p8 (&a)[kNP], const Pieces (
 
 namespace {
 
-constexpr int kTasks = 14;
-constexpr int kTargetWG = 760;   // ~3 rounds of one workgroup per CU (short tail)
-// the gathering kernels (a sample list, gathered inputs): 1024 measured 1.5%
-// faster than 760 at cfg2's fine pass (three alternating rounds, profiles/r04/abalt_tw)
-constexpr int kTargetWGGather = 1024;
-// the LDS-DMA kernel (wgrad4_kernel, one workgroup per CU) over a sample list:
-// 1536 measured 3% faster than 1024 (768: +0.5%, 2048: -1.5%) at cfg2's fine
-// pass (two alternating rounds, profiles/r05/ab/u_*)
-constexpr int kTargetWGW4 = 1536;
-constexpr int kMax2(int x, int y) { return x > y ? x : y; }
-[[maybe_unused]] constexpr int kTargetWGMax = kMax2(kMax2(kTargetWG, kTargetWGGather), kTargetWGW4);
 constexpr int kThreads = 512;    // 8 waves: two per SIMD, so one wave's staging and
                                  // barrier time overlaps its partner's MFMAs
 
-enum SegKind { SEG_ACC = 0, SEG_PE = 1, SEG_DPE = 2, SEG_HEAD = 3 };
-
-// f16x3: the task pairs that read the same saved segment (wgrad_launch:
-// DZ(4), H(7), dz_dir) run fused -- one workgroup stages the shared segment
-// once and computes both outputs.
+// f16x3: the task pairs that read the same saved segment (wgrad_plan.h
+// kFused: DZ(4), H(7), dz_dir) run fused -- one workgroup stages the shared
+// segment once and computes both outputs.  Compile time: it sizes the kernels' LDS.
 constexpr bool kFuse = NR_F16 || NR_BF1;
-// bit i: pair i of wgrad_launch's kFused (f16x3 6: no spills, measured slower)
-constexpr int kFuseMask = 7;
-// the same for the gathering kernels (the *_active entry points): the fused
-// PE pair (bit 0) leaves wgrad3_kernel<true, ROWS> 33 spilled VGPRs (8
-// without it), and unfused its fine-pass launch runs 1.97 -> 1.83 ms
-// (three alternating same-box rounds, profiles/r04/abalt_fuse6)
-constexpr int kFuseMaskGather = 6;
 
 // flat parameter offsets, NeRF.named_parameters() order (packing.py param_offsets)
 struct POff {
@@ -166,6 +148,35 @@ __device__ __forceinline__ int wg_m(const WgArgs& a) {
 __device__ __forceinline__ int wg_nact(const WgArgs& a) {
     return a.slist ? (wg_m(a) + 31) / 32 : a.nb;
 }
+
+// workgroup c's slab of task T
+__device__ __forceinline__ float* wg_slab(const WgArgs& a, const WgTask& T, int c) {
+    return a.slab + T.slab + (int64_t)c * (T.a.width * T.b.width + T.a.width);
+}
+// the dispatch position whose workgroups include this one
+__device__ __forceinline__ int wg_task(const WgArgs& a) {
+    int t = 0;
+#pragma unroll 1
+    while (t + 1 < kTasks && (int)blockIdx.x >= a.wg_start[t + 1]) ++t;
+    return t;
+}
+// What every kernel's workgroup starts from: its index c among its task's G
+// workgroups, the task, its blocks [b0, b1) of the split-K partition, and its
+// slab (a fused partner's: wg_slab of a.task[T.fuse] at the same c)
+struct WgWork {
+    int c;
+    const WgTask& T;
+    int b0, b1;
+    float* slab;
+    __device__ __forceinline__ explicit WgWork(const WgArgs& a) : WgWork(a, wg_task(a)) {}
+    __device__ __forceinline__ WgWork(const WgArgs& a, int t)
+        : c(blockIdx.x - a.wg_start[t]), T(a.task[t]) {
+        const int nact = wg_nact(a);
+        b0 = (int)((int64_t)c * nact / T.G);
+        b1 = (int)((int64_t)(c + 1) * nact / T.G);
+        slab = wg_slab(a, T, c);
+    }
+};
 
 // f16x3: the gradient operand of a task is scaled by 2^(kWT - e(max |dz|)) so
 // its largest element sits in [2^kWT, 2^(kWT+1)) < 65504; the input operand

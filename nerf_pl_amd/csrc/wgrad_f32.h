@@ -203,15 +203,7 @@ __device__ __forceinline__ void wgrad_body(const WgArgs& a, const WgTask& T, int
 template <bool GA, bool ROWS>
 __global__ void __launch_bounds__(kThreads, 2) wgrad_kernel(WgArgs a) {
     __shared__ __attribute__((aligned(16))) float lds[2 * kBuf];   // 144 KiB
-    int t = 0;
-#pragma unroll 1
-    while (t + 1 < kTasks && (int)blockIdx.x >= a.wg_start[t + 1]) ++t;
-    const int c = blockIdx.x - a.wg_start[t];
-    const WgTask& T = a.task[t];
-    const int nact = wg_nact(a);
-    const int b0 = (int)((int64_t)c * nact / T.G);
-    const int b1 = (int)((int64_t)(c + 1) * nact / T.G);
-    float* slab = a.slab + T.slab + (int64_t)c * (T.a.width * T.b.width + T.a.width);
+    const auto [c, T, b0, b1, slab] = WgWork(a);
     // task shapes (see nr_wgrad's task list); wave-uniform
     // (WM, WN) = wave grid over the task's output (<= 8 waves; 128 accumulators max)
     switch (__builtin_amdgcn_readfirstlane(T.id)) {

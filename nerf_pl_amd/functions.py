@@ -26,8 +26,10 @@ from ._lib import call, stream_of
 def _wgrad_workspace(device_index: int, stream: int = 0) -> torch.Tensor:
     """Split-K slab workspace of the weight gradient, one per (device, stream):
     backward passes enqueued on different streams never share slabs.  The
-    size is the library's bound over every launch shape (~1.2 GB; the slabs a
-    launch uses depend only on the task list, not on n).  At most 4 are kept
+    size is the library's largest launch plan over every arithmetic and path
+    (276 MiB, computed from the plan itself, csrc/wgrad_plan.h; a launch's
+    slabs stop growing with n once every task has its full workgroup count,
+    so one size serves every n).  At most 4 are kept
     (least recently used evicted): a workspace is allocated while its stream is
     current, so once evicted the caching allocator hands its memory only to
     later work on that same stream, which runs after the kernels still using

@@ -5,7 +5,7 @@
 # -> ablibs/libnerf_pl_amd_<name>.so (selected at run time with NERF_PL_AMD_LIB)
 # (wgrad.hip has no experiment defines left -- NR_W3_* / NR_W4_* / NR_WGRAD_TARGET_WG*
 # / NR_WGRAD_FUSE_MASK* were last accepted by commit d1ec9da; to A/B its tuned
-# constants, edit wgrad_common.h in a second checkout)
+# constants, edit wgrad_plan.h in a second checkout)
 # (mlp_fwd3 / mlp_bwd3 still accept NR_BWD_W2 only; commit 0be27df last accepted their other defines)
 set -eu
 name=$1; objs_ab=$2; flags=$3; kind=${4:-h3}
