@@ -7,6 +7,12 @@ per ``NeRF`` parameter (views into one flat buffer, named_parameters order).
 
 ``_Composite``: volume compositing forward/backward (``nr_composite_*``, with
 the disparity map ``nr_composite_disp_*``).
+
+When the rays require grad both also return the gradients of
+``rays`` and ``z`` (``nr_raygrad_mlp`` / ``nr_composite_raygrad``), and
+``_CoarseZ`` / ``_MergedZ`` make the depths functions of the rays: stratified
+depths in near / far (``nr_coarse_z_raygrad``), the coarse depths' places in
+the merged fine row (``nr_merge_raygrad``).  Nothing of this runs otherwise.
 """
 from __future__ import annotations
 
@@ -141,17 +147,22 @@ class _FusedMLP(torch.autograd.Function):
     @staticmethod
     def forward(ctx, model, rays, z, spr, x, sigma_only, *params):
         train = any(ctx.needs_input_grad[6:])
+        # rays that require grad (or depths that do: they are functions of the
+        # rays) run the training forward and the data gradient whether or not a
+        # parameter trains; the weight gradient runs for trainable parameters only
+        ray_grad = x is None and (ctx.needs_input_grad[1] or ctx.needs_input_grad[2])
+        bwd = train or ray_grad
         if train and sigma_only and x is not None:
             raise NotImplementedError("nerf_pl_amd: training NeRF.forward(x, sigma_only=True) on "
                                       "pre-embedded input is not supported; use render_rays")
-        packed_f, packed_b = model.packed(backward=train)
+        packed_f, packed_b = model.packed(backward=bwd)
         # a sigma-only graph (rendering_shadows.py:167) trains through the
         # sigma-only training kernels (layers 1-8 and the sigma head: no
         # xyz_encoding_final / dir / rgb work), in every arithmetic
-        so_train = train and sigma_only and SIGMA_TRAIN_KERNELS and x is None
-        kern_sigma_only = sigma_only and (not train or so_train)
+        so_train = bwd and sigma_only and SIGMA_TRAIN_KERNELS and x is None
+        kern_sigma_only = sigma_only and (not bwd or so_train)
         defer = False
-        if train and x is None and ACTIVE_SAMPLES and ops.arith_of(packed_b) in ACTIVE_ARITHS:
+        if bwd and x is None and ACTIVE_SAMPLES and ops.arith_of(packed_b) in ACTIVE_ARITHS:
             if DEFER_SAVE == "all" or (DEFER_SAVE in ("sigma", "auto") and so_train):
                 defer = True
             elif DEFER_SAVE == "auto":
@@ -164,12 +175,12 @@ class _FusedMLP(torch.autograd.Function):
             rays = ops._dev(rays, "rays", 8)
             z = ops._dev(z, "z")
         out, save = ops.mlp_forward(packed_f, rays=rays, z=z, samples_per_ray=spr, x=x,
-                                    sigma_only=kern_sigma_only, save=train and not defer)
+                                    sigma_only=kern_sigma_only, save=bwd and not defer)
         if _DEBUG is not None and save is not None:
             # the training forward's saved activations, in call order (tests
             # read the ReLU masks the kernels chose: tests/grad64.py mlp_flips)
             _DEBUG.setdefault("fwd_saves", []).append((save, out.shape[0], ops.MATH))
-        if train:
+        if bwd:
             # the flat parameters the forward ran with (the dir layer's
             # feat-column weight gradient reads W_final, b_final and W_dir
             # there: nr_wgrad_dir_feat), and the parameters themselves, so that
@@ -180,14 +191,16 @@ class _FusedMLP(torch.autograd.Function):
             flat = model.flat_params()
             if defer:     # the backward recomputes the listed samples' activations
                 ctx.save_for_backward(out, rays, z, packed_f, packed_b, flat, *params)
-                ctx.spr = spr
             else:
-                ctx.save_for_backward(out, save, packed_f, packed_b, flat, *params)
+                ctx.save_for_backward(out, save, packed_f, packed_b, flat, *params,
+                                      *((rays, z) if ray_grad else ()))
+            ctx.spr = spr
+            ctx.train, ctx.ray_grad = train, ray_grad
             ctx.defer = defer
             ctx.sigma_only = sigma_only
             ctx.model = model if DEFER_SAVE == "auto" else None
             ctx.so_kernels = so_train
-        if sigma_only and train and out.shape[1] == 4:
+        if sigma_only and bwd and out.shape[1] == 4:
             out = out[:, 3:4].contiguous()
         return out
 
@@ -227,16 +240,29 @@ class _FusedMLP(torch.autograd.Function):
         grad_ws = torch.empty(ops.n_blocks(n) * ops.GRAD_PER_BLOCK, device=dev)
         call(ops.entry("nr_mlp_bwd" + sfx, packed_b), packed_b.data_ptr(), ops.head_ptr(packed_f),
              out.data_ptr(), g_out.data_ptr(), save.data_ptr(), n, grad_ws.data_ptr(), *lst, st)
-        gflat = torch.empty(packing.N_PARAMS, device=dev)
-        ws = _wgrad_workspace(dev.index, int(st))
-        call(ops.entry("nr_wgrad" + sfx, packed_b), save.data_ptr(), grad_ws.data_ptr(), n,
-             ws.data_ptr(), gflat.data_ptr(), *lst, st)
-        if not so:
-            _dir_feat(flat, gflat, st)
+        gflat = None
+        if ctx.train:
+            gflat = torch.empty(packing.N_PARAMS, device=dev)
+            ws = _wgrad_workspace(dev.index, int(st))
+            call(ops.entry("nr_wgrad" + sfx, packed_b), save.data_ptr(), grad_ws.data_ptr(), n,
+                 ws.data_ptr(), gflat.data_ptr(), *lst, st)
+            if not so:
+                _dir_feat(flat, gflat, st)
+        g_rays = g_z = None
+        if ctx.ray_grad:
+            if not ctx.defer:
+                rays, z = ctx.saved_tensors[-2:]
+            # the MLP's input gradient from dz1, dz5, dz_dir;
+            # a frozen network stops here: no weight gradient, every p.grad None
+            g_rays, g_smp = ops.mlp_ray_gradient(flat, grad_ws, rays, z, int(ctx.spr),
+                                                 ops.arith_of(packed_b), so, lst)
+            g_rays = g_rays if ctx.needs_input_grad[1] else None
+            g_z = g_smp[:, 3] if ctx.needs_input_grad[2] else None
         if _DEBUG is not None:
             _DEBUG.update(save=save, grad_ws=grad_ws, g_out=g_out, gflat=gflat, n=n)
             _DEBUG.setdefault("g_outs", []).append(g_out)
-        return (None,) * 6 + _param_grads(gflat, ctx.sigma_only)
+        pgrads = _param_grads(gflat, ctx.sigma_only) if ctx.train else (None,) * len(_SHAPES)
+        return (None, g_rays, g_z, None, None, None) + pgrads
 
 
 def _sample_list(ctx, g_out, n, st):
@@ -280,7 +306,8 @@ def mlp_apply(model, *, rays=None, z=None, spr=0, x=None, sigma_only=False):
     params = model.ordered_params()
     if z is not None:
         z = z.reshape(-1)
-    if not any(p.requires_grad for p in params) or not torch.is_grad_enabled():
+    ray_grad = x is None and any(t is not None and t.requires_grad for t in (rays, z))
+    if not (any(p.requires_grad for p in params) or ray_grad) or not torch.is_grad_enabled():
         packed_f, _ = model.packed()
         out, _ = ops.mlp_forward(packed_f, rays=rays, z=z, samples_per_ray=spr, x=x,
                                  sigma_only=sigma_only)
@@ -313,14 +340,23 @@ class _Composite(torch.autograd.Function):
     def backward(ctx, *g):   # (g_rgb, g_depth, g_opac[, g_disp], g_w): weights not differentiable
         raw, z, rays, noise = ctx.saved_tensors[:4]
         has_noise, noise_std, seed, stream, white_back, disp = ctx.cfg
-        g_raw = ops.composite_backward(raw, z, rays, noise if has_noise else None, noise_std, seed,
-                                       stream, white_back, *g[:-1], *ctx.saved_tensors[4:],
-                                       disp=disp)
-        return (g_raw,) + (None,) * 8
+        noise = noise if has_noise else None
+        g_raw = g_z = g_rays = None
+        if ctx.needs_input_grad[0]:
+            g_raw = ops.composite_backward(raw, z, rays, noise, noise_std, seed, stream,
+                                           white_back, *g[:-1], *ctx.saved_tensors[4:], disp=disp)
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+            # the depths' and the direction norm's part of the ray gradient
+            g_z, g_rays = ops.composite_ray_gradient(raw, z, rays, noise, noise_std, seed, stream,
+                                                     white_back, *g[:-1], *ctx.saved_tensors[4:],
+                                                     disp=disp)
+            g_z = g_z if ctx.needs_input_grad[1] else None
+            g_rays = g_rays if ctx.needs_input_grad[2] else None
+        return (g_raw, g_z, g_rays) + (None,) * 6
 
 
 def composite_apply(raw, z, rays, noise, noise_std, seed, stream, white_back, disp=False):
-    if torch.is_grad_enabled() and raw.requires_grad:
+    if torch.is_grad_enabled() and (raw.requires_grad or z.requires_grad or rays.requires_grad):
         return _Composite.apply(raw, z, rays, noise, noise_std, seed, stream, white_back, disp)
     return ops.composite_forward(raw, z, rays, noise, noise_std, seed, stream, white_back,
                                  disp=disp)
@@ -328,3 +364,54 @@ def composite_apply(raw, z, rays, noise, noise_std, seed, stream, white_back, di
 
 def composite_disp_apply(*args):
     return composite_apply(*args, disp=True)
+
+
+class _CoarseZ(torch.autograd.Function):
+    """The stratified depths (rendering.py:216-232) as a function of the rays'
+    near and far columns."""
+
+    @staticmethod
+    def forward(ctx, rays, n_samples, use_disp, perturb, u, seed):
+        ctx.save_for_backward(rays, u if u is not None else torch.empty(0))
+        ctx.cfg = (n_samples, use_disp, perturb, u is not None, seed)
+        return ops.coarse_z(rays, n_samples, use_disp, perturb, u=u, seed=seed)
+
+    @staticmethod
+    def backward(ctx, g_z):
+        rays, u = ctx.saved_tensors
+        n_samples, use_disp, perturb, has_u, seed = ctx.cfg
+        g_rays = ops.coarse_z_ray_gradient(rays, n_samples, use_disp, perturb,
+                                           u if has_u else None, seed, g_z)
+        return (g_rays,) + (None,) * 5
+
+
+def coarse_z_apply(rays, n_samples, use_disp, perturb, u=None, seed=0):
+    if torch.is_grad_enabled() and rays.requires_grad:
+        return _CoarseZ.apply(rays, n_samples, use_disp, perturb, u, seed)
+    return ops.coarse_z(rays, n_samples, use_disp, perturb, u=u, seed=seed)
+
+
+class _MergedZ(torch.autograd.Function):
+    """z_fine = sort(cat[z_coarse, z_pdf.detach()]) (rendering.py:253-257) as a
+    function of z_coarse: the importance depths' own dependence on the weights
+    and on near / far is detached, as the reference detaches it."""
+
+    @staticmethod
+    def forward(ctx, z_coarse, weights, rays, n_importance, u, jitter, seed):
+        _, z_fine = ops.sample_pdf(weights, rays, n_importance, u=u, jitter=jitter, seed=seed,
+                                   z_coarse=z_coarse, merge=True)
+        ctx.save_for_backward(z_coarse, z_fine)
+        return z_fine
+
+    @staticmethod
+    def backward(ctx, g_zf):
+        z_coarse, z_fine = ctx.saved_tensors
+        return (ops.merge_ray_gradient(z_coarse, z_fine, g_zf),) + (None,) * 6
+
+
+def merged_z_apply(z_coarse, weights, rays, n_importance, u, jitter, seed):
+    if torch.is_grad_enabled() and z_coarse.requires_grad:
+        return _MergedZ.apply(z_coarse, weights, rays.detach(), n_importance, u, jitter, seed)
+    _, z_fine = ops.sample_pdf(weights, rays, n_importance, u=u, jitter=jitter, seed=seed,
+                               z_coarse=z_coarse, merge=True)
+    return z_fine

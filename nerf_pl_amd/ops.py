@@ -313,6 +313,71 @@ def sample_pdf(weights, rays, n_importance, u=None, jitter=None, seed=0, z_coars
     return z_pdf, z_fine
 
 
+# ---- gradients with respect to the rays (include/nerf_pl_amd_raygrad.h) ----
+# layout of the dz rows in grad_ws per arithmetic (csrc/raygrad.hip rg_chunk)
+_RAYGRAD_LAYOUT = {"fp32": 0, "bf16x6": 1, "f16x3": 1, "bf16": 2}
+
+
+def mlp_ray_gradient(flat, grad_ws, rays, z, samples_per_ray, arith, sigma_only, lst=()):
+    """The MLP's input gradient from the data gradient's ``grad_ws``: (g_rays
+    (R, 8), g_samples (n, 8)) with g_samples[:, 3] = d loss / d z.  ``lst``:
+    the (samples, count) device addresses of the backward's sample list, or
+    () for every sample; unlisted samples contribute exact zeros."""
+    from ._lib_raygrad import call as rcall
+    n_rays, n = rays.shape[0], z.numel()
+    dev = rays.device
+    g_smp = (torch.zeros if lst else torch.empty)(n, 8, device=dev)
+    g_rays = torch.empty(n_rays, 8, device=dev)
+    st = stream_of(dev)
+    rcall("nr_raygrad_mlp", ptr(flat), ptr(grad_ws), ptr(rays), ptr(z), n, int(samples_per_ray),
+          n_rays, _RAYGRAD_LAYOUT[arith], int(sigma_only), *(lst or (None, None)), ptr(g_smp), st)
+    rcall("nr_raygrad_reduce", ptr(g_smp), ptr(z), n_rays, int(samples_per_ray), ptr(g_rays), st)
+    return g_rays, g_smp
+
+
+def composite_ray_gradient(raw, z, rays, noise, noise_std, seed, rng_stream, white_back,
+                           g_rgb, g_depth, g_opacity, g_disp=None, depth=None, opacity=None,
+                           disp=False):
+    """composite_backward's arguments -> (g_z (R, S), g_rays (R, 8)): the
+    compositing's gradient in the depths and, through |d|, in the directions."""
+    from ._lib_raygrad import call as rcall
+    del disp
+    n_rays, S = z.shape
+    g_z = torch.empty(n_rays, S, device=z.device)
+    g_rays = torch.empty(n_rays, 8, device=z.device)
+    stride = raw.shape[-1]
+    grads = (g_rgb, g_depth, g_opacity, g_disp, depth, opacity)
+    rcall("nr_composite_raygrad", ptr(raw), stride, stride - 1, ptr(z), ptr(rays), ptr(noise),
+          float(noise_std), seed, rng_stream, n_rays, S, int(white_back),
+          *(ptr(None if t is None else t.contiguous()) for t in grads), ptr(g_z), ptr(g_rays),
+          stream_of(z.device))
+    return g_z, g_rays
+
+
+def merge_ray_gradient(z_coarse, z_fine, g_zfine):
+    """g_zcoarse (R, S): each coarse depth's gradient from its place in the
+    merged fine row (nr_sample_pdf puts a coarse depth first on a tie)."""
+    from ._lib_raygrad import call as rcall
+    n_rays, S = z_coarse.shape
+    g_zfine = _dev(g_zfine, "g_zfine")
+    g = torch.empty(n_rays, S, device=z_coarse.device)
+    rcall("nr_merge_raygrad", ptr(z_coarse), ptr(z_fine), ptr(g_zfine), n_rays, S,
+          z_fine.shape[1] - S, ptr(g), stream_of(z_coarse.device))
+    return g
+
+
+def coarse_z_ray_gradient(rays, n_samples, use_disp, perturb, u, seed, g_z):
+    """g_rays (R, 8), columns 6..7: coarse_z's depths in near and far."""
+    from ._lib_raygrad import call as rcall
+    n_rays = rays.shape[0]
+    g_z = _dev(g_z, "g_z")
+    g_rays = torch.empty(n_rays, 8, device=rays.device)
+    tl = linspace_table(n_samples, rays.device.index)
+    rcall("nr_coarse_z_raygrad", ptr(rays), ptr(tl), n_rays, n_samples, int(use_disp),
+          float(perturb), ptr(u), seed, ptr(g_z), ptr(g_rays), stream_of(rays.device))
+    return g_rays
+
+
 def embed(x, n_freqs):
     x = _dev(x, "x", 3)
     n = x.shape[0]

@@ -14,6 +14,11 @@ Drop-in notes
   embeddings or NeRF configuration takes the composable path (the reference's
   ``inference`` sequence -- xyz, embeddings, model -- on device GEMMs), with
   sampling and compositing on the same HIP kernels either way.
+* ``rays`` may require grad (pose refinement, light-pose optimisation): the
+  fused path leaves in ``rays.grad`` the gradient the reference's autograd
+  would, trainable or frozen networks alike.  The composable
+  path does not carry that gradient and raises instead of returning a partial
+  one.
 * Everything runs on the HIP device that holds ``rays``.  A batch on the host
   (BASELINE configs[0], "PyTorch CPU, plumbing") runs nerf_pl_amd.host: the
   reference's sequence in PyTorch CPU ops, as the reference itself runs on
@@ -28,7 +33,7 @@ import os
 import torch
 
 from . import ops
-from .functions import composite_apply, mlp_apply
+from .functions import coarse_z_apply, composite_apply, merged_z_apply, mlp_apply
 from .rng import (STREAM_JITTER, STREAM_NOISE_COARSE, STREAM_NOISE_FINE, STREAM_PERTURB,
                   STREAM_U, PhiloxRNG, TorchRNG)
 
@@ -156,6 +161,11 @@ def _render_rays(models, embeddings, rays, N_samples, use_disp, perturb, noise_s
         return _composable_mlp(model, embeddings, rays, z, spr, sigma_only)
 
     rays = ops._dev(rays, "rays", 8)
+    if not fused and rays.requires_grad and torch.is_grad_enabled():
+        raise NotImplementedError(
+            "nerf_pl_amd.render_rays: the composable path (a non-default NeRF or Embedding) does "
+            "not produce the gradient with respect to the rays; detach them, or use the default "
+            "NeRF() with [Embedding(3, 10), Embedding(3, 4)]")
     dev = rays.device
     n_rays = rays.shape[0]
     if n_rays == 0 and not empty_ok:
@@ -180,7 +190,7 @@ def _render_rays(models, embeddings, rays, N_samples, use_disp, perturb, noise_s
 
     # stratified coarse depths (rendering.py:216-232)
     u1 = rng.rand((n_rays, N_samples), dev) if perturb > 0 else None
-    z_c = ops.coarse_z(rays, N_samples, use_disp, perturb, u=u1, seed=seed)
+    z_c = coarse_z_apply(rays, N_samples, use_disp, perturb, u=u1, seed=seed)
     noise_c = rng.randn((n_rays, N_samples), dev)
 
     cap = _capture if _capture is not None else {}
@@ -203,8 +213,7 @@ def _render_rays(models, embeddings, rays, N_samples, use_disp, perturb, noise_s
         # sample_pdf + sort(cat[z, z_pdf]) (rendering.py:253-257), weights detached
         u = rng.rand((n_rays, N_importance), dev)
         jit = rng.rand((n_rays, N_importance), dev)
-        _, z_f = ops.sample_pdf(w_c.detach(), rays, N_importance, u=u, jitter=jit, seed=seed,
-                                z_coarse=z_c, merge=True)
+        z_f = merged_z_apply(z_c, w_c.detach(), rays, N_importance, u, jit, seed)
         cap["z_fine"] = z_f
         s_f = N_samples + N_importance
 

@@ -80,6 +80,10 @@ def render_rays_sharded(models, embeddings, rays, N_samples=64, use_disp=False, 
     that rendered each row.  ``N_importance`` must be the same on every rank
     (checked: ``sharded_map`` raises on mismatched outputs)."""
     from .distributed import sharded_map
+    if isinstance(rays, torch.Tensor) and rays.requires_grad and torch.is_grad_enabled():
+        raise NotImplementedError(
+            "nerf_pl_amd.render_rays_sharded: the sharded render does not produce the gradient "
+            "with respect to the rays; detach them, or call render_rays on every rank")
 
     def fn(r, rng=rng):
         return render_rays(models, embeddings, r.contiguous(), N_samples, use_disp, perturb,
