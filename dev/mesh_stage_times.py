@@ -46,6 +46,7 @@ def main():
     ap.add_argument("--views", type=int, default=4)
     ap.add_argument("--img", type=int, default=400)
     ap.add_argument("--N_samples", type=int, default=64)
+    ap.add_argument("--N_importance", type=int, default=64)
     ap.add_argument("--repeats", type=int, default=3)
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -59,7 +60,8 @@ def main():
     poses = torch.stack([pose_spherical(360.0 * k / a.views, -30.0, 4.0) for k in range(a.views)])
     focal = blender_focal(a.img)
     res = {"N": a.N, "quantile": a.quantile, "views": a.views, "img": a.img,
-           "N_samples": a.N_samples, "repeats": a.repeats, "ms": {}, "all_ms": {}}
+           "N_samples": a.N_samples, "N_importance": a.N_importance, "repeats": a.repeats,
+           "ms": {}, "all_ms": {}}
 
     def stage(name, fn):
         out, med, ms = timed(fn, a.repeats)
@@ -75,8 +77,17 @@ def main():
     cv, ct = stage("largest_cluster", lambda: extract.largest_cluster(w, t))
     res["V_cluster"], res["T_cluster"] = len(cv), len(ct)
     # colours for every vertex of the mesh (the largest piece of a noise field is small)
+    w = w.contiguous()
     stage("fuse_vertex_colors", lambda: extract.fuse_vertex_colors(
-        model, w.contiguous(), poses, images, focal, 2.0, a.N_samples))
+        model, w, poses, images, focal, 2.0, a.N_samples))
+    # the --use_vertex_normal branch on the same vertices: the CSR list and the
+    # normals kernel, the ray kernel, then all of it with the coarse + fine render
+    coarse = NeRF().to(dev)
+    coarse.load_state_dict(O.make_params(2, sigma_bias=0.5))
+    normals = stage("vertex_normals", lambda: extract.vertex_normals(w, t))
+    stage("normal_rays", lambda: extract.normal_rays(w, normals, 2.0, 6.0))
+    stage("color_by_vertex_normals", lambda: extract.color_by_vertex_normals(
+        [coarse, model], w, t, 2.0, 6.0, a.N_samples, a.N_importance))
     print(json.dumps(res))
 
 

@@ -9,11 +9,16 @@ Colour mesh extraction (extract_color_mesh.py:142-297) follows on the device,
 without mcubes, open3d, cv2 or plyfile: ``marching_cubes`` ->
 ``grid_to_world`` -> ``largest_cluster`` -> ``fuse_vertex_colors`` ->
 ``write_ply``, chained by ``extract_color_mesh`` (kernels: csrc/mesh.hip,
-declared in include/nerf_pl_amd_mesh.h).  Three parities with the replaced
-libraries are *unpinned*, because none of them is available to test against:
-PyMCubes' vertex order and winding, open3d's triangle connectivity, and
-cv2.remap's fixed-point bilinear weights; each function says what it does
-instead.
+declared in include/nerf_pl_amd_mesh.h).  The ``--use_vertex_normal`` branch
+(lines 187-204, 280-281) colours the same mesh from the two networks alone:
+``vertex_normals`` -> ``normal_rays`` -> the coarse + fine ``render_rays``,
+chained by ``color_by_vertex_normals`` (kernels: csrc/mesh_normals.hip,
+declared in include/nerf_pl_amd_mesh_normals.h).  Five parities with the
+replaced libraries are *unpinned*, because none of them is available to test
+against: PyMCubes' vertex order and winding, open3d's triangle connectivity,
+cv2.remap's fixed-point bilinear weights, open3d's vertex-normal rule, and
+the side of the surface the reference's normal rays look at (it follows from
+PyMCubes' winding); each function says what it does instead.
 """
 from __future__ import annotations
 
@@ -22,7 +27,7 @@ import functools
 import numpy as np
 import torch
 
-from . import _lib_mesh, ops
+from . import _lib_mesh, _lib_mesh_normals, ops
 from ._lib import ptr, stream_of
 from .mesh_tables import MC_ROW, MC_TRI_TABLE
 
@@ -255,7 +260,8 @@ def fuse_vertex_colors(model_fine, vertices, poses, images, focal, near, N_sampl
     weights and border-clamped neighbours; ``cv2.remap``'s 1/32-pixel
     fixed-point weights and its rounding to uint8 per view are not
     reproduced -- parity *unpinned* (cv2 is not available to compare with).
-    ``--use_vertex_normal`` (lines 187-204) is not implemented.
+    The ``--use_vertex_normal`` branch (lines 187-204) is
+    ``color_by_vertex_normals``.
 
     ``return_opacity``: also return the float64 colours before quantisation
     (n,3) and the per-view opacities (n_views, n)."""
@@ -297,21 +303,160 @@ def fuse_vertex_colors(model_fine, vertices, poses, images, focal, near, N_sampl
     return colors
 
 
+# ---------------------------------------------------------------------------
+# vertex colours along the vertex normals (extract_color_mesh.py:187-204, 280-281)
+# ---------------------------------------------------------------------------
+def _mesh(vertices, triangles):
+    vertices = ops._dev(vertices, "vertices", 3)
+    if not isinstance(triangles, torch.Tensor) or triangles.dtype != torch.int32 \
+            or triangles.dim() != 2 or triangles.shape[1] != 3 \
+            or triangles.device != vertices.device:
+        raise ValueError("triangles: expected a (T, 3) int32 tensor on the vertices' device")
+    if vertices.dim() != 2:
+        raise ValueError(f"vertices: expected (V, 3), got {tuple(vertices.shape)}")
+    return vertices, triangles.contiguous()
+
+
+@torch.no_grad()
+def vertex_normals(vertices: torch.Tensor, triangles: torch.Tensor) -> torch.Tensor:
+    """Unit vertex normals (V,3) float64 of the indexed device mesh
+    ``vertices`` (V,3) float32 / ``triangles`` (T,3) int32 with indices in
+    ``[0, V)`` -- ``mesh.compute_vertex_normals()`` of
+    extract_color_mesh.py:189.
+
+    A triangle's normal is the unnormalised ``(v1 - v0) x (v2 - v0)`` in
+    float64, so the sum over a vertex's triangles is area-weighted; the sum is
+    divided by its Euclidean norm, and a NaN quotient -- a zero sum, a vertex
+    no triangle lists, a sum holding NaN or Inf from NaN vertices -- becomes
+    ``(0, 0, 1)``.  That is open3d's rule as recalled; parity with open3d is
+    *unpinned* (the library is not available to compare with).
+
+    The sum is a gather: a stable ``argsort`` of the corner list groups the
+    corners by vertex in ascending corner index ``3t + k``, ``bincount`` and
+    an exclusive ``cumsum`` give each vertex's row, and one kernel
+    (``nr_mesh_vertex_normals``) has one thread per vertex add the cross
+    products of its row in that order.  Nothing is atomic, so two runs give
+    bit-identical tensors.  With ``marching_cubes``' winding the normals point
+    from the occupied side to the empty side."""
+    vertices, triangles = _mesh(vertices, triangles)
+    dev, n_v, n_t = vertices.device, vertices.shape[0], triangles.shape[0]
+    normals = torch.empty(n_v, 3, dtype=torch.float64, device=dev)
+    if n_v == 0:
+        return normals
+    if n_v >= 2 ** 31 or 3 * n_t >= 2 ** 31:
+        raise ValueError(f"vertex_normals: {n_v} vertices / {n_t} triangles do not fit int32 "
+                         "indices")
+    offsets = torch.zeros(n_v + 1, dtype=torch.int64, device=dev)
+    inc = None
+    if n_t:
+        flat = triangles.reshape(-1).to(torch.int64)
+        counts = torch.bincount(flat, minlength=n_v)           # raises on a negative index
+        if counts.numel() != n_v:
+            raise ValueError(f"triangles: vertex index {counts.numel() - 1} for {n_v} vertices")
+        offsets[1:] = torch.cumsum(counts, 0)
+        inc = (torch.argsort(flat, stable=True) // 3).to(torch.int32)
+    _lib_mesh_normals.call("nr_mesh_vertex_normals", ptr(vertices),
+                           ptr(triangles) if n_t else None, ptr(offsets),
+                           ptr(inc) if n_t else None, n_v, n_t, ptr(normals), stream_of(dev))
+    return normals
+
+
+@torch.no_grad()
+def normal_rays(vertices, normals, near, far, near_t=1.0, inward=True) -> torch.Tensor:
+    """The rays (V,8) float32 ``[o, d, near, far]`` of
+    extract_color_mesh.py:190-193, 200 for ``vertices`` (V,3) float32 and
+    ``normals`` (V,3) float64 (``nr_mesh_normal_rays``, float32 in the
+    reference's order): ``d = float32(normal)`` and
+    ``o = v - d * near * near_t``, so the sample at ``z = near * near_t`` is
+    the vertex itself and the ray travels on along ``d``.
+
+    ``inward=True`` negates the normal first.  The reference's ray runs along
+    ``+normal``, and the method sees the object's colour only if that
+    direction enters the object; ``marching_cubes`` here winds every triangle
+    so that the normal points from the occupied side to the empty side, and
+    whether PyMCubes does is *unpinned*.  So the default points the ray into
+    the occupied side; ``inward=False`` applies the reference's lines to the
+    normals as they are."""
+    vertices = ops._dev(vertices, "vertices", 3)
+    n = vertices.shape[0]
+    if not isinstance(normals, torch.Tensor) or normals.dtype != torch.float64 \
+            or normals.shape != (n, 3) or normals.device != vertices.device:
+        raise ValueError(f"normals: expected a ({n}, 3) float64 tensor on the vertices' device")
+    normals = normals.contiguous()
+    rays = torch.empty(n, 8, device=vertices.device)
+    _lib_mesh_normals.call("nr_mesh_normal_rays", ptr(vertices), ptr(normals), n, float(near),
+                           float(far), float(near_t), int(bool(inward)), ptr(rays),
+                           stream_of(vertices.device))
+    return rays
+
+
+@torch.no_grad()
+def color_by_vertex_normals(models, vertices, triangles, near, far, N_samples=64, N_importance=64,
+                            near_t=1.0, white_back=False, inward=True, chunk=FUSE_CHUNK,
+                            return_rgb=False, *, rng=None):
+    """uint8 colours (V,3) of the mesh's vertices from ``models = [coarse,
+    fine]`` alone -- the ``--use_vertex_normal`` branch,
+    extract_color_mesh.py:187-204 and 280-284: one ray per vertex along its
+    normal (``vertex_normals``, ``normal_rays``; see there for ``inward`` and
+    the two unpinned parities), rendered coarse + fine with
+    ``render_rays(models, ..., N_samples, False, 0, 0, N_importance, chunk,
+    white_back, test_time=True, rng=rng)``, ``chunk`` vertices per call, in
+    order; the colour is ``(rgb_fine * 255).to(uint8)``.  Nothing else draws
+    from torch's generator.  ``return_rgb``: also return the float32
+    ``rgb_fine`` (V,3)."""
+    from . import Embedding, render_rays
+    if len(models) != 2:
+        raise ValueError("color_by_vertex_normals: models = [coarse, fine]")
+    if chunk < 1:
+        raise ValueError(f"color_by_vertex_normals: chunk = {chunk}")
+    vertices, triangles = _mesh(vertices, triangles)
+    n = vertices.shape[0]
+    if n:
+        rays = normal_rays(vertices, vertex_normals(vertices, triangles), near, far, near_t, inward)
+        embeddings = [Embedding(3, 10), Embedding(3, 4)]
+        rgb = torch.cat([
+            render_rays(models, embeddings, rays[i:i + chunk], N_samples, False, 0, 0,
+                        N_importance, chunk, white_back, test_time=True, rng=rng)["rgb_fine"]
+            for i in range(0, n, chunk)], 0)
+    else:
+        rgb = torch.empty(0, 3, device=vertices.device)
+    colors = (rgb * 255).to(torch.uint8)
+    return (colors, rgb) if return_rgb else colors
+
+
 @torch.no_grad()
 def extract_color_mesh(model_fine, poses, images, focal, near, N=256, x_range=(-1.0, 1.0),
                        y_range=(-1.0, 1.0), z_range=(-1.0, 1.0), sigma_threshold=20.0,
                        N_samples=64, occ_threshold=0.2, white_back=False, return_opacity=False, *,
-                       _capture=None):
+                       _capture=None, use_vertex_normal=False, model_coarse=None, far=None,
+                       N_importance=64, near_t=1.0, inward=True):
     """extract_color_mesh.py:113-284 in one call: ``sigma_grid`` ->
     ``marching_cubes`` -> ``grid_to_world`` -> ``largest_cluster`` ->
     ``fuse_vertex_colors``.  Returns ``(vertices (V,3) float32 world,
     triangles (T,3) int32, colors (V,3) uint8)``; with ``return_opacity`` the
     float64 colours and per-view opacities of ``fuse_vertex_colors`` follow.
-    Hand the first three to ``write_ply``."""
+    Hand the first three to ``write_ply``.
+
+    ``use_vertex_normal=True`` (the reference's ``--use_vertex_normal``) ends
+    the chain with ``color_by_vertex_normals([model_coarse, model_fine], ...,
+    near, far, N_samples, N_importance, near_t, white_back, inward)`` instead:
+    ``model_coarse`` and ``far`` are then required, ``poses``, ``images`` and
+    ``focal`` are not read and may be ``None``, and there are no opacities to
+    return."""
+    if use_vertex_normal:
+        if model_coarse is None or far is None:
+            raise ValueError("extract_color_mesh: use_vertex_normal needs model_coarse and far")
+        if return_opacity:
+            raise ValueError("extract_color_mesh: use_vertex_normal has no per-view opacities")
     sigma = sigma_grid(model_fine, N, x_range, y_range, z_range)
     vertices, triangles = marching_cubes(sigma, sigma_threshold)
     vertices = grid_to_world(vertices, N, x_range, y_range, z_range)
     vertices, triangles = largest_cluster(vertices, triangles)
+    if use_vertex_normal:
+        vertices = vertices.contiguous()
+        colors = color_by_vertex_normals([model_coarse, model_fine], vertices, triangles, near, far,
+                                         N_samples, N_importance, near_t, white_back, inward)
+        return vertices, triangles, colors
     out = fuse_vertex_colors(model_fine, vertices.contiguous(), poses, images, focal, near,
                              N_samples, occ_threshold, white_back, return_opacity,
                              _capture=_capture)
@@ -320,11 +465,13 @@ def extract_color_mesh(model_fine, poses, images, focal, near, N=256, x_range=(-
     return vertices, triangles, out
 
 
-def write_ply(path, vertices, triangles, colors=None) -> None:
+def write_ply(path, vertices, triangles, colors=None, normals=None) -> None:
     """Binary little-endian PLY as extract_color_mesh.py:286-297 writes it
     through plyfile: vertex ``x y z`` float32 (+ ``red green blue`` uchar with
-    ``colors``), face ``vertex_indices`` as ``list uchar int``.  numpy only;
-    tensors (any device) or arrays."""
+    ``colors``), face ``vertex_indices`` as ``list uchar int``.  With
+    ``normals`` (V,3), ``nx ny nz`` follow ``x y z`` as float32, before the
+    colours (the reference writes none).  numpy only; tensors (any device) or
+    arrays."""
     def arr(a, dtype):
         if isinstance(a, torch.Tensor):
             a = a.detach().cpu().numpy()
@@ -335,6 +482,12 @@ def write_ply(path, vertices, triangles, colors=None) -> None:
     fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
     header = ["ply", "format binary_little_endian 1.0", f"element vertex {len(v)}",
               "property float x", "property float y", "property float z"]
+    if normals is not None:
+        nrm = arr(normals, "<f4").reshape(-1, 3)
+        if len(nrm) != len(v):
+            raise ValueError(f"write_ply: {len(nrm)} normals for {len(v)} vertices")
+        fields += [("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")]
+        header += ["property float nx", "property float ny", "property float nz"]
     if colors is not None:
         c = arr(colors, "u1").reshape(-1, 3)
         if len(c) != len(v):
@@ -345,6 +498,9 @@ def write_ply(path, vertices, triangles, colors=None) -> None:
     vert = np.empty(len(v), dtype=fields)
     for k, name in enumerate("xyz"):
         vert[name] = v[:, k]
+    if normals is not None:
+        for k, name in enumerate(("nx", "ny", "nz")):
+            vert[name] = nrm[:, k]
     if colors is not None:
         for k, name in enumerate(("red", "green", "blue")):
             vert[name] = c[:, k]
