@@ -108,6 +108,88 @@ def llff_ndc_rays(img_w: int = 504, img_h: int = 378, n_poses: int = 4,
     return torch.cat(out, 0)
 
 
+def _gen_rays(c2w, n_poses, H, W, focal, near, far, sel, n, ndc, ndc_near, rgb_pool):
+    """the ``nr_gen_rays`` launch: (rays, rgb_out or None)"""
+    from ._lib import call, ptr, stream_of
+    dev = c2w.device
+    rays = torch.empty(n, 8, device=dev)
+    rgb_out = torch.empty(n, 3, device=dev) if rgb_pool is not None else None
+    call("nr_gen_rays", ptr(c2w), n_poses, H, W, float(W / 2), float(H / 2), float(focal),
+         float(near), float(far), int(ndc), float(ndc_near), -1. / (W / (2. * focal)),
+         -1. / (H / (2. * focal)), 2. * ndc_near, ptr(sel), n, ptr(rgb_pool), ptr(rgb_out),
+         ptr(rays), stream_of(dev))
+    return rays, rgb_out
+
+
+def pose_gradient(c2w: torch.Tensor, H: int, W: int, focal: float, g_rays: torch.Tensor,
+                  sel: torch.Tensor = None, ndc: bool = False, ndc_near: float = 1.0,
+                  with_focal: bool = False):
+    """The transpose of ``generate_rays`` (``nr_gen_rays_posegrad``, DESIGN.md
+    20): from ``g_rays`` (n, 8), the gradient of a loss in the rays that
+    ``generate_rays(c2w, H, W, focal, ., ., sel, ndc, ndc_near)`` returned, the
+    gradient in ``c2w`` (n_poses, 3, 4) and, ``with_focal``, one float64 focal
+    partial per pose (n_poses), else None.  Columns 6..7 of ``g_rays`` are not
+    read.  Deterministic: two calls give identical buffers."""
+    from . import ops
+    from ._lib import ptr, stream_of
+    from ._lib_posegrad import call
+    c2w = ops._dev(c2w.detach(), "c2w")
+    if c2w.shape[-2:] != (3, 4):
+        raise ValueError(f"c2w must be (n_poses, 3, 4), got {tuple(c2w.shape)}")
+    dev = c2w.device
+    n_poses = c2w.reshape(-1, 12).shape[0]
+    if sel is not None:
+        sel = sel.to(device=dev, dtype=torch.int64).contiguous()
+    n = sel.shape[0] if sel is not None else n_poses * H * W
+    g_rays = ops._dev(g_rays, "g_rays", 8)
+    if g_rays.shape != (n, 8):
+        raise ValueError(f"g_rays must be ({n}, 8), got {tuple(g_rays.shape)}")
+    if g_rays.data_ptr() % 16:
+        g_rays = g_rays.clone()
+    if n == 0:      # an empty tensor has no address to pass; the gradient of no ray is zero
+        return (torch.zeros(n_poses, 3, 4, device=dev),
+                torch.zeros(n_poses, dtype=torch.float64, device=dev) if with_focal else None)
+    g_c2w = torch.empty(n_poses, 3, 4, device=dev)
+    g_focal = torch.empty(n_poses, dtype=torch.float64, device=dev) if with_focal else None
+    focal = float(focal)
+    call("nr_gen_rays_posegrad", ptr(c2w), n_poses, H, W, float(W / 2), float(H / 2), focal,
+         int(ndc), float(ndc_near), -1. / (W / (2. * focal)), -1. / (H / (2. * focal)),
+         2. * ndc_near, ptr(sel), n, ptr(g_rays), ptr(g_c2w), ptr(g_focal), stream_of(dev))
+    return g_c2w, g_focal
+
+
+class _GenRays(torch.autograd.Function):
+    """``nr_gen_rays`` as a function of the poses and the focal length: the
+    forward is the launch of the plain path (same rays, bit for bit), the
+    backward is ``nr_gen_rays_posegrad``."""
+
+    @staticmethod
+    def forward(ctx, c2w, focal_t, focal, H, W, near, far, sel, ndc, ndc_near, rgb_pool):
+        n_poses = c2w.reshape(-1, 12).shape[0]
+        n = sel.shape[0] if sel is not None else n_poses * H * W
+        rays, rgb_out = _gen_rays(c2w, n_poses, H, W, focal, near, far, sel, n, ndc, ndc_near,
+                                  rgb_pool)
+        ctx.save_for_backward(c2w, sel)
+        ctx.geom = (H, W, focal, ndc, ndc_near)
+        ctx.focal_meta = None if focal_t is None else (focal_t.device, focal_t.shape)
+        if rgb_out is not None:
+            ctx.mark_non_differentiable(rgb_out)
+        return rays, rgb_out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_rays, _g_rgb):
+        c2w, sel = ctx.saved_tensors
+        H, W, focal, ndc, ndc_near = ctx.geom
+        want_c2w, want_focal = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        g_c2w, g_focal = pose_gradient(c2w, H, W, focal, g_rays, sel, ndc, ndc_near,
+                                       with_focal=want_focal)
+        if want_focal:      # the float64 sum of the per-pose partials
+            device, shape = ctx.focal_meta
+            g_focal = g_focal.sum().to(torch.float32).to(device).reshape(shape)
+        return (g_c2w.reshape(c2w.shape) if want_c2w else None, g_focal) + (None,) * 9
+
+
 def generate_rays(c2w: torch.Tensor, H: int, W: int, focal: float, near: float, far: float,
                   sel: torch.Tensor = None, ndc: bool = False, ndc_near: float = 1.0,
                   rgb_pool: torch.Tensor = None):
@@ -118,9 +200,25 @@ def generate_rays(c2w: torch.Tensor, H: int, W: int, focal: float, near: float, 
     means every pixel of every pose.  With ``rgb_pool`` (n_poses*H*W, 3) the
     target colours of the same pixels are returned too.  With ``ndc`` the
     forward-facing transform (get_ndc_rays, near plane ``ndc_near``) is applied
-    and near/far become 0/1 (llff.py:236-242)."""
+    and near/far become 0/1 (llff.py:236-242).
+
+    The rays differentiate in the poses, as the reference's ``get_rays`` /
+    ``get_ndc_rays`` do: when ``c2w`` requires grad (an ``nn.Parameter``, or any
+    ``c2w = f(params)`` composed in torch) the same launch runs inside an
+    ``autograd.Function`` whose backward is ``nr_gen_rays_posegrad`` (DESIGN.md
+    20).  ``focal`` may also be a one-element float32 tensor; if it requires
+    grad it receives the float64 sum of the per-pose partials.  Its value is
+    read once on the host for the kernel's scalar arguments, so a
+    device-resident focal costs a synchronisation per call: keep it a CPU
+    scalar parameter.  Colours (``rgb_out``) carry no gradient.  When neither
+    requires grad nothing new runs and ``rays.grad_fn`` is None."""
     from . import ops
-    from ._lib import call, ptr, stream_of
+    focal_t = None
+    if isinstance(focal, torch.Tensor):
+        if focal.numel() != 1 or focal.dtype != torch.float32:
+            raise TypeError("focal: a float or a one-element float32 tensor, got "
+                            f"{tuple(focal.shape)} {focal.dtype}")
+        focal_t, focal = focal, focal.item()
     c2w = ops._dev(c2w.to(torch.float32), "c2w")
     if c2w.shape[-2:] != (3, 4):
         raise ValueError(f"c2w must be (n_poses, 3, 4), got {tuple(c2w.shape)}")
@@ -131,17 +229,17 @@ def generate_rays(c2w: torch.Tensor, H: int, W: int, focal: float, near: float, 
         n = sel.shape[0]
     else:
         n = n_poses * H * W
-    rays = torch.empty(n, 8, device=dev)
-    rgb_out = None
     if rgb_pool is not None:
         rgb_pool = ops._dev(rgb_pool, "rgb_pool", 3)
-        rgb_out = torch.empty(n, 3, device=dev)
     if ndc:
         near, far = 0.0, 1.0
-    call("nr_gen_rays", ptr(c2w), n_poses, H, W, float(W / 2), float(H / 2), float(focal),
-         float(near), float(far), int(ndc), float(ndc_near), -1. / (W / (2. * focal)),
-         -1. / (H / (2. * focal)), 2. * ndc_near, ptr(sel), n, ptr(rgb_pool), ptr(rgb_out),
-         ptr(rays), stream_of(dev))
+    if torch.is_grad_enabled() and (c2w.requires_grad
+                                    or (focal_t is not None and focal_t.requires_grad)):
+        rays, rgb_out = _GenRays.apply(c2w, focal_t, focal, H, W, near, far, sel, ndc, ndc_near,
+                                       rgb_pool)
+    else:
+        rays, rgb_out = _gen_rays(c2w, n_poses, H, W, focal, near, far, sel, n, ndc, ndc_near,
+                                  rgb_pool)
     return (rays, rgb_out) if rgb_pool is not None else rays
 
 
