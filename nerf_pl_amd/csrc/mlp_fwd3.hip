@@ -70,7 +70,7 @@ __device__ __forceinline__ void head_dot(const f32x4 (&acc)[NF][NS], const float
 #pragma unroll
         for (int S = 0; S < NS; ++S)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) p[S] = fmaf(RELU ? relu_i(acc[F][S][r]) : acc[F][S][r], v[r], p[S]);
+            for (int r = 0; r < 4; ++r) p[S] = fmaf(RELU ? relu_keep(acc[F][S][r]) : acc[F][S][r], v[r], p[S]);
     }
 #pragma unroll
     for (int S = 0; S < NS; ++S) p[S] = sum_over_groups(p[S]);
@@ -244,8 +244,8 @@ struct AccU {
         constexpr int s = SC::value;
         x0 = acc_b(X, s, sb, 2 * p);
         x1 = acc_b(X, s, sb, 2 * p + 1);
-        if constexpr (RELU) { x0 = relu_i(x0); x1 = relu_i(x1); }
-        if constexpr (kWScale != 0) { x0 *= kWUnscale; x1 *= kWUnscale; }   // exact
+        if constexpr (RELU) { x0 = relu_unscale(x0); x1 = relu_unscale(x1); }   // exact; keeps a NaN
+        else if constexpr (kWScale != 0) { x0 *= kWUnscale; x1 *= kWUnscale; }   // exact
         if constexpr (SIG) {
             // (units run s-major, sb = 0 before 1: wsg[(s + 1) & 1][p] was
             // last read by unit (s - 1, 1, p))
@@ -551,7 +551,7 @@ __global__ void __launch_bounds__(64 * kWaves, 1) mlp_fwd3_kernel(Fwd3Args a) {
                 for (int S = 0; S < kNS; ++S) {
                     f32x4 v = C[F][S];
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) v[r] = relu_i(v[r]) * kWUnscale;
+                    for (int r = 0; r < 4; ++r) v[r] = relu_unscale(v[r]);
                     store_row<128>(v, F, S, hd, lane);
                     mask_bits(v, F, S, w);
                 }

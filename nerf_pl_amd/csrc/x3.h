@@ -355,6 +355,31 @@ __device__ __forceinline__ float wave_max(float x) {
 __device__ __forceinline__ float relu_i(float x) {
     return __int_as_float(max(__float_as_int(x), 0));
 }
+// relu(x) * 2^-kWScale, the forward's step from a layer's accumulator to the
+// next layer's input.  f16x3: (|x| + x) * k / 2, exact for a power of two k
+// and the same two VALU operations as max and multiply -- but a NaN stays a
+// NaN.  relu_i (like v_max_f32) takes a negative NaN to 0, and the matrix
+// cores' Inf - Inf comes back with its sign bit set: an activation past fp16's
+// range (hi = Inf, lo = -Inf) or a packed weight of 2^16 would otherwise turn
+// into a finite wrong output instead of a non-finite one (a
+// pre-activation of -Inf becomes NaN as well).  The other arithmetics have
+// fp32's exponent range and keep the integer max.
+__device__ __forceinline__ float relu_unscale(float x) {
+#if NR_F16
+    constexpr float h = 0.5f * kWUnscale;
+    return fmaf(fabsf(x), h, x * h);
+#else
+    return relu_i(x);
+#endif
+}
+// relu(x) with the accumulator's scale kept (the heads' dot products)
+__device__ __forceinline__ float relu_keep(float x) {
+#if NR_F16
+    return fmaf(fabsf(x), 0.5f, x * 0.5f);
+#else
+    return relu_i(x);
+#endif
+}
 
 // the weight pieces of one output tile of a k-group
 struct Frag { p8 p[kNP]; };
