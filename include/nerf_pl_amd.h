@@ -455,8 +455,15 @@ int nr_sm_normed_depth_bwd(const float* camera, const float* pixels, const float
  * the run's first camera) or one eye/camera for all (per_ray=0), the light
  * camera (3,3) + eye (3) and the light's normed depth map light_w (res_w*res_h)
  * -> out (n,3) = shadow value + out_eps.  method 1: clip(max(d/delta, epsilon));
- * method 2: per-run min-max normalisation (+ sigmoid).  workspace:
- * nr_sm_workspace_bytes(n, res_w*res_h) bytes; keep it for nr_sm_backward. */
+ * method 2: per-run min-max normalisation (+ sigmoid).  The texel of a ray is
+ * light_w[(int)v * res_h + (int)u] with u clamped to [0, res_w-1] and v to
+ * [0, res_h-1] (the reference's w_light.view(w, h)[v, u]; res_h <= res_w).
+ * Non-finite texels behave as in torch: under method 1 a NaN texel makes only
+ * the rays that read it NaN; under method 2 the run's min and max propagate
+ * NaN, so a NaN difference anywhere in a run makes that whole run NaN (and its
+ * depth and light-map gradients in nr_sm_backward).  Depths must be finite.
+ * workspace: nr_sm_workspace_bytes(n, res_w*res_h) bytes; keep it for
+ * nr_sm_backward. */
 int64_t nr_sm_workspace_bytes(int64_t n, int64_t n_light);
 int nr_sm_forward(const float* pixels, const float* depth, const float* eye, const float* cameras,
                   int per_ray, const float* light_camera, const float* light_eye,

@@ -11,7 +11,8 @@
 //                       camera, clamped nearest-texel gather of the light's
 //                       normed depth map, shadow_method_1 output or the raw
 //                       difference for shadow_method_2
-//   sm_minmax_kernel    shadow_method_2: per-run min / max (one wave per run)
+//   sm_minmax_kernel    shadow_method_2: per-run min / max (one wave per run;
+//                       NaN if any difference of the run is NaN, as torch's)
 //   sm_norm_kernel      shadow_method_2: min-max normalisation, clip
 //   backward: sm_bwd_reduce_kernel (per-run sums of the normalisation
 //   gradient) + sm_bwd_kernel (d loss / d camera depth, and each ray's
@@ -202,13 +203,21 @@ __global__ void __launch_bounds__(256) sm_minmax_kernel(int n, SmWs ws) {
         const int s = base + __ffsll((unsigned long long)starts) - 1;
         starts &= starts - 1;
         float mn = INFINITY, mx = -INFINITY;
+        bool nan = false;
         for (int j0 = s;; j0 += 64) {
             const int j = j0 + lane;
             const bool in = j < n && ws.run[j] == s;
-            if (in) { const float v = ws.t[j]; mn = fminf(mn, v); mx = fmaxf(mx, v); }
+            if (in) {
+                const float v = ws.t[j];
+                mn = fminf(mn, v); mx = fmaxf(mx, v);
+                nan |= v != v;
+            }
             if (!__all(in)) break;
         }
         mn = wmin(mn); mx = wmax(mx);
+        // tensor.min() / max() propagate NaN, fminf / fmaxf drop it: one NaN
+        // difference makes the run's min and max NaN, and with them the whole run
+        if (__any(nan)) mn = mx = __builtin_nanf("");
         if (lane == 0) { ws.mm[2 * s] = mn; ws.mm[2 * s + 1] = mx; }
     }
 }

@@ -32,6 +32,12 @@ many random draws to commit; they store each draw's kind, shape and checksum
 and the test re-draws them from the recorded seed with the CPU generator
 (``draws_seed``), checking the checksums first.
 
+``options`` (``tests/golden/shadow_options/options.npz``, outside the listing
+of ``tests/golden/shadow``) pins the option branches no training-step case
+takes: the reference's own ``run_shadow_mapping`` on 64 rays of one pose
+against a 16x16 light map with ``sigmoid=True`` under shadow_method_2,
+``epsilon=0.25, delta=0.5`` and ``delta=0.05`` under shadow_method_1.
+
     python tests/golden/make_golden_shadow.py [case ...]   # default: all
 """
 from __future__ import annotations
@@ -282,6 +288,52 @@ CASES = {
 }
 
 
+OPTION_RUNS = {
+    "m2_sigmoid": dict(mode="shadow_method_2", sigmoid=True),
+    "m1_eps025_delta05": dict(mode="shadow_method_1", epsilon=0.25, delta=0.5),
+    "m1_delta005": dict(mode="shadow_method_1", delta=0.05),
+}
+
+
+def run_options(ref):
+    """The reference's run_shadow_mapping under the options of OPTION_RUNS."""
+    _, rs, camera_mod = ref
+    import models.efficient_shadow_mapping as esm
+    wh, n = 16, 64
+    light, _, pixels, cams = scene(wh, camera_mod.Camera)
+    cam = cams[0][0]
+    g = torch.Generator().manual_seed(91)
+    # rays whose reprojection stays 0.05 texel clear of a truncation edge, so
+    # that another host's last-bit differences cannot move a texel
+    pix, dep = [], []
+    while len(pix) < n:
+        p = pixels[torch.randint(0, wh * wh, (1,), generator=g)].float()
+        d = 2 + 4 * torch.rand(1, generator=g)
+        K = esm.get_projections(cam, light, torch.cat([p, d.view(1, 1)], 1), "cpu")[0, :2]
+        if all((0.05 <= k - torch.floor(k) <= 0.95 and 0 < k < wh - 1) or k < -0.05
+               or k > wh - 0.95 for k in K):
+            pix.append(p); dep.append(d)
+    mesh = torch.cat([torch.cat(pix), torch.cat(dep).view(-1, 1)], 1)
+    # half of the texels within the range of wl, half wide enough for delta = 0.5
+    narrow = 0.08 + 0.12 * torch.rand(wh * wh, generator=g)
+    wide = -0.5 + 1.1 * torch.rand(wh * wh, generator=g)
+    lw = torch.where(torch.rand(wh * wh, generator=g) < 0.5, narrow, wide)
+    light_mesh = torch.cat([pixels.float(), lw.view(-1, 1)], 1)
+    out = {"pixels": mesh[:, :3].numpy(), "depth": mesh[:, 3].numpy(),
+           "eye_pos": cam.eye_pos.numpy(), "camera": cam.camera.numpy(),
+           "light_eye": light.eye_pos.numpy(), "light_camera": light.camera.numpy(),
+           "light_w": lw.numpy(), "res": np.array([wh, wh], dtype=np.int64)}
+    for name, kw in OPTION_RUNS.items():
+        sm = esm.run_shadow_mapping((wh, wh), cam, light, mesh, light_mesh, "cpu", **kw)
+        out["out_" + name] = sm.numpy()
+        inside = ((sm[:, 0] > 0) & (sm[:, 0] < 1)).float().mean()
+        print(f"options/{name}: {float(inside):.2f} of rays strictly inside (0, 1)")
+    os.makedirs(OUT + "_options", exist_ok=True)
+    path = os.path.join(OUT + "_options", "options.npz")
+    np.savez_compressed(path, **out)
+    print(f"options: {os.path.getsize(path) / 1024:.1f} KiB")
+
+
 def augment_bound64(name):
     """Add the *_bound64 / *_pbound64 noise floors to a committed fixture
     without rewriting its arrays (for fixtures written on another host, whose
@@ -319,7 +371,10 @@ def main():
     import models.camera as camera_mod             # noqa: E402
     import models.rendering_shadows as rs          # noqa: E402
     ref = (ref_nerf, rs, camera_mod)
-    for name in sys.argv[1:] or list(CASES):
+    for name in sys.argv[1:] or list(CASES) + ["options"]:
+        if name == "options":
+            run_options(ref)
+            continue
         wh, runs, S, I, LI, method, kw = CASES[name]
         run_case(ref, name, wh, runs, S, I, LI, method, **kw)
 
