@@ -38,21 +38,42 @@ import os
 
 import torch
 
-from .optim import FusedAdam
+from .optim import FusedAdam, FusedRAdam, FusedRanger, FusedSGD
 
 __all__ = ["PipelinedStep"]
 
 
 class PipelinedStep:
-    def __init__(self, models, lr=5e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
-                 reducer=None):
+    def __init__(self, models, lr=5e-4, betas=None, eps=1e-8, weight_decay=0.0,
+                 reducer=None, optimizer="adam", **optimizer_kwargs):
+        """``optimizer``: adam | sgd | radam | ranger, the pair of fused
+        optimizers of that kind (one per model); ``optimizer_kwargs`` go to
+        their constructors (``momentum``; ``degenerated_to_sgd``; ``alpha``,
+        ``k``, ``N_sma_threshhold``).  ``betas=None`` is the optimizer's own
+        default: (0.9, 0.999), Ranger's (.95, .999)."""
         from . import rendering
         if len(models) != 2:
             raise ValueError("PipelinedStep: a (coarse, fine) model pair")
         self.models = models
-        kw = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
-        self.opt_c = FusedAdam([p for p in models[0].parameters() if p.requires_grad], **kw)
-        self.opt_f = FusedAdam([p for p in models[1].parameters() if p.requires_grad], **kw)
+        if optimizer == "adam":
+            if optimizer_kwargs:
+                raise TypeError(f"PipelinedStep: unexpected arguments {sorted(optimizer_kwargs)}")
+            cls, kw = FusedAdam, dict(lr=lr, betas=(0.9, 0.999) if betas is None else betas,
+                                      eps=eps, weight_decay=weight_decay)
+        elif optimizer == "sgd":
+            if betas is not None:
+                raise TypeError("PipelinedStep: SGD has no betas")
+            cls, kw = FusedSGD, dict(lr=lr, weight_decay=weight_decay, **optimizer_kwargs)
+        elif optimizer in ("radam", "ranger"):
+            cls = FusedRAdam if optimizer == "radam" else FusedRanger
+            kw = dict(lr=lr, eps=eps, weight_decay=weight_decay, **optimizer_kwargs)
+            if betas is not None:
+                kw["betas"] = betas
+        else:
+            raise ValueError(f"PipelinedStep: optimizer {optimizer!r} is not one of "
+                             "adam, sgd, radam, ranger")
+        self.opt_c = cls([p for p in models[0].parameters() if p.requires_grad], **kw)
+        self.opt_f = cls([p for p in models[1].parameters() if p.requires_grad], **kw)
         self.reducer = reducer
         if reducer is not None:
             if len(reducer.buckets) != 2:
